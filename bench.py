@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 128 --warmup 8            (default: N=1, finishes in minutes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py --gpus 1 --steps 128 --warmup 8 --dump-outputs DIR   (also writes the last timed step's logits / token)
 
 Workload (BASELINE.json metric "decode tokens/sec Llama-3.2-3B batch=1"): Llama-3.2-3B, fp16 GGUF
 weights kept fp16 in HBM, fp32 activations and fp32 KV cache (the reference's precision), batch-1
@@ -57,7 +58,27 @@ def parse():
                                                          "entry as configs[0]; none = only the headline")
     ap.add_argument("--child", action="store_true", help="(internal) one `configs[]` entry: compact object, bounded CPU work")
     ap.add_argument("--sample-tokens", type=int, default=64, help="tokens of the sampling-path (decode_topk + host nucleus) and blocking-greedy timings (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (logits.npy: float32 [V]; token.npy: the greedy token as "
+                         "float64 [1]) to DIR; the inputs are seeded, so two builds run with the same arguments can be compared output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs is supported with --gpus 1 only")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """DIR/<name>.npy for every array (float32 / float64 only, 64 MB in all)."""
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 Q4_K, Q6_K = 12, 14
@@ -333,7 +354,9 @@ def run_single(args):
     ev_ms = mgr.TimerEnd()
     mgr.Synchronize()
     wall = time.perf_counter() - t0
-    toks = m.FetchTokens(args.steps)
+    toks = m.FetchTokens(1)   # the last timed step's token (the device keeps the last 8192; --steps may exceed that)
+    if args.dump_outputs:     # before the profiling below overwrites the logits
+        dump_outputs(args.dump_outputs, {"logits": m.Read(4, dims.V), "token": toks.astype(np.float64)})
     ms_per_step = ev_ms / args.steps
     value = args.steps / (ev_ms / 1e3)
     # ---- roofline: dominant kernel = the fused RMSNorm + Wgate/Wup GEMV + SiLU*up launch

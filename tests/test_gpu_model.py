@@ -657,7 +657,7 @@ def test_engine_pipeline_stages_and_fallback(mgr):
 
 
 @pytest.mark.parametrize("quant", ["f16", "q4_k_m"])
-def test_full_size_parity_through_bench(quant):
+def test_full_size_parity_through_bench(quant, tmp_path):
     """The whole Llama-3.2-3B (BASELINE config 3: 28 blocks, vocabulary 128256, 6.4 GB of fp16 weights) at full size: `bench.py`
     runs the oracle on the same weights (its `cpu_baseline` leg, here 6 tokens) and compares EVERY position's full logit vector
     with the GPU's, and compares the 512-token MFMA prefill with the token-by-token decode path.  The tolerances are the
@@ -671,10 +671,15 @@ def test_full_size_parity_through_bench(quant):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "16", "--warmup", "2", "--cpu-tokens", "6", "--quant", quant],
-                       env=env, cwd=root, capture_output=True, text=True, timeout=1500)
+    dump = str(tmp_path / "outputs")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "16", "--warmup", "2", "--cpu-tokens", "6", "--quant", quant,
+                        "--dump-outputs", dump], env=env, cwd=root, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+    # --dump-outputs: what the last timed step returned, its greedy token being the argmax of its logits
+    lg, tk = np.load(os.path.join(dump, "logits.npy")), np.load(os.path.join(dump, "token.npy"))
+    assert lg.dtype == np.float32 and lg.shape == (synth.BY_NAME["llama-3.2-3b"].V,) and np.isfinite(lg).all()
+    assert tk.dtype == np.float64 and tk.shape == (1,) and int(tk[0]) == int(np.argmax(lg))
     cb = d["cpu_baseline"]
     tol = 5e-4 * max(1.0, cb["max_abs_logit"])             # observed 4e-5 at 3B fp16 (logits are O(1) here), 2.3e-5 as Q4_K_M
     assert cb["kind"] == "port" and cb["max_abs_logit_diff_vs_gpu_token0"] <= tol
