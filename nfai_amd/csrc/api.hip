@@ -214,6 +214,27 @@ NFAI_API int32_t nfai_hip_ctx_xcd_shares(nfai_ctx_t h, uint16_t *shares8, float 
     return NFAI_OK;
 }
 
+// Test hooks (not in nfai_hip.h): force the XCD dealing shares of a context, call before a model on it is finalised (gemv_base reads
+// them when the token graph is captured).  shares8 != nullptr: these 8 shares, taken as given (the launch's own range check is what a
+// test exercises), also for the op-level GEMV entries (nfai_hip_gemv, _gemv_fused, _lmhead_argmax, _gemv_gateup_silu), which
+// otherwise never deal; nullptr: dealing off, as NFAI_XCD_DEAL=0.
+NFAI_API int32_t nfai_hip_debug_xcd_shares(nfai_ctx_t h, const uint16_t *shares8)
+{
+    CTX_OR_FAIL(c, h);
+    if (shares8) {
+        for (int x = 0; x < 8; x++) c->xcd_shares[x] = shares8[x];
+        c->xcd_state = 1;
+        c->xcd_ops = true;
+    } else {
+        c->xcd_state = 2;
+        c->xcd_ops = false;
+    }
+    return NFAI_OK;
+}
+
+// GEMV launches that took the XD instantiations (rows dealt by share) since the library was loaded, on any context.
+NFAI_API uint64_t nfai_hip_debug_gemv_dealt(void) { return gemv_dealt_launches(); }
+
 static int canary_check_all(Ctx *c);  // NFAI_HIP_DEBUG_CANARY (below, with nfai_hip_buf_alloc)
 
 NFAI_API int32_t nfai_hip_ctx_synchronize(nfai_ctx_t h)
@@ -563,6 +584,7 @@ NFAI_API int32_t nfai_hip_gemv(nfai_ctx_t h, nfai_buf_t W, int32_t type, nfai_bu
     a.K = K;
     a.mode = GEMV_PLAIN;
     a.y = static_cast<float *>(by->ptr) + y_off;
+    if (c->xcd_ops) a.xcd_shares = c->xcd_shares;   // nfai_hip_debug_xcd_shares
     return gemv_common(c, a, __func__);
 }
 
@@ -894,6 +916,7 @@ NFAI_API int32_t nfai_hip_gemv_fused(nfai_ctx_t h, nfai_buf_t W, int32_t type, n
     a.mode = br ? GEMV_RESIDUAL : GEMV_PLAIN;
     a.res = br ? static_cast<const float *>(br->ptr) : nullptr;
     a.y = static_cast<float *>(by->ptr);
+    if (c->xcd_ops) a.xcd_shares = c->xcd_shares;   // nfai_hip_debug_xcd_shares
     return gemv_common(c, a, __func__);
 }
 
@@ -931,6 +954,7 @@ NFAI_API int32_t nfai_hip_lmhead_argmax(nfai_ctx_t h, nfai_buf_t W, int32_t type
     // workspace: its own range of the context scratch (ticket word zero between launches)
     a.argmax_part = static_cast<char *>(c->scratch) + SCR_LMHEAD;
     a.argmax_out = static_cast<uint32_t *>(bo->ptr);
+    if (c->xcd_ops) a.xcd_shares = c->xcd_shares;   // nfai_hip_debug_xcd_shares
     return gemv_common(c, a, __func__);
 }
 
@@ -967,6 +991,7 @@ NFAI_API int32_t nfai_hip_gemv_gateup_silu(nfai_ctx_t h, nfai_buf_t Wg, nfai_buf
     a.K = K;
     a.mode = GEMV_GATEUP;
     a.y = static_cast<float *>(by->ptr);
+    if (c->xcd_ops) a.xcd_shares = c->xcd_shares;   // nfai_hip_debug_xcd_shares
     return gemv_common(c, a, __func__);
 }
 

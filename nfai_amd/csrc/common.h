@@ -52,6 +52,7 @@ struct Ctx {
     int xcd_state = 0;
     uint16_t xcd_shares[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float xcd_probe_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // mean end of a workgroup of each label in the probe launch (equal shares)
+    bool xcd_ops = false;  // test hook (nfai_hip_debug_xcd_shares): the op-level GEMV entries pass xcd_shares as gemv_base does
     hipStream_t stream = nullptr;
     bool owns_stream = true;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -149,6 +150,7 @@ bool gemv_begin_ok(const GemvArgs &a);                         // can this q|k|v
 // Measures how fast the workgroups of each blockIdx % 8 label (= one XCD each) stream from HBM with every CU streaming, and derives
 // the dealing shares of GemvArgs::xcd_shares; nullptr when switched off (NFAI_XCD_DEAL=0) or when the probe could not run.
 const uint16_t *gemv_xcd_calibrate(Ctx *c);
+uint64_t gemv_dealt_launches();  // k_gemv launches that took the XD instantiations (GemvParams::xd.S != 0) since the library was loaded
 hipError_t launch_gemv_kq(const GemvArgs &a, hipStream_t s);  // Q4_K (native blocks) / Q6_K (plane layout)
 hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s); // Q4_K_T16: MFMA dot products
 hipError_t launch_repack_q4k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <vector>
 
@@ -729,6 +730,9 @@ static GemvPlan plan_gemv(uint32_t NU, uint32_t K, int epl, int rpu, uint32_t n_
     return pl;
 }
 
+static std::atomic<uint64_t> g_dealt{0};   // launches of the XD instantiations (nfai_hip_debug_gemv_dealt: tests prove the path was taken)
+uint64_t gemv_dealt_launches() { return g_dealt.load(); }
+
 template <int WT, int MODE, int UPW, int U, bool GUARD>
 static hipError_t launch_one(const GemvParams &p, const GemvPlan &pl, hipStream_t s)
 {
@@ -744,6 +748,7 @@ static hipError_t launch_one(const GemvParams &p, const GemvPlan &pl, hipStream_
                 hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, true, false, true>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, s, p);
             else
                 hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, false, false, true>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, s, p);
+            g_dealt++;
             return hipGetLastError();
         }
     }

@@ -714,12 +714,9 @@ def test_full_size_parity_through_bench(quant, tmp_path):
     assert "blocks [28,32) of 32" in cfgs[2]["workload"]
 
 
-def test_timed_region_full_depth_against_the_oracle():
-    """the benchmark's own timed region against the oracle at full depth — the whole Llama-3.2-3B (28 blocks, fp16,
-    V = 128256), a 512-token prompt through the MFMA prefill, then 8 greedy tokens on the decode path (positions 512..519), against
-    `OracleLlama` fed the same 520 tokens one by one in fp32 (the reference's loop, LlamaModel.cs:103-126; ~60 s on 16 host
-    threads).  The prefill rounds its GEMM operands to fp16, so the bar is the stated fp16 tolerance on the logits
-    (2e-2 * max(1, max|logit|), about 1e-1 absolute here) with identical greedy tokens at every step; the oracle skips the lm_head for the prompt."""
+def _timed_region_run(quant, T=512, G=8):
+    """The benchmark's timed region on the whole Llama-3.2-3B with bench.py's weights (same generator, same seed): a T-token
+    prompt through the MFMA prefill, then G greedy tokens on the decode path.  -> (weights, prompt, [G + 1 logit vectors], tokens)."""
     import torch
     import bench as B
     from nfai_amd import _lib
@@ -727,9 +724,8 @@ def test_timed_region_full_depth_against_the_oracle():
     from nfai_amd.llama_model import LlamaModel
     dims = synth.LLAMA_32_3B
     torch.cuda.set_device(0)
-    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant="f16")
+    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant=quant)
     mgr = HipBufferManager(0)
-    T, G = 512, 8
     C = T + G + 1
     m = LlamaModel(mgr, synth.make_metadata(dims), B.as_model_tensors(_lib, weights), C, max_batch=T,
                    dims=dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0))
@@ -743,21 +739,75 @@ def test_timed_region_full_depth_against_the_oracle():
         toks.append(am)
     assert m.Pos == T + G
     m.Dispose()
-    ref = orc.OracleLlama(odesc(dims, C), B.host_weights(weights))
-    del weights
-    for t in prompt[:-1]:
-        ref.step(int(t), want_logits=False)
-    want = ref.step(int(prompt[-1]))
-    worst = 0.0
-    for i in range(G + 1):
-        err, scale = float(np.abs(got[i] - want).max()), max(1.0, float(np.abs(want).max()))
-        worst = max(worst, err / scale)
-        assert err <= 2e-2 * scale, (i, err, scale)
-        assert orc.argmax(want) == toks[i], (i, orc.argmax(want), toks[i])
-        if i < G:
-            want = ref.step(toks[i])
-    print(f"full-depth timed region: worst max|dlogit| / max(1, max|logit|) over {G + 1} positions = {worst:.3g}")
     mgr.Dispose()
+    return weights, prompt, got, toks
+
+
+def _timed_region_child(quant, out_dir):
+    """Child-process side of test_timed_region_full_depth_against_the_oracle (switches read once per process, e.g.
+    NFAI_PREFILL_FUSED): the G + 1 logit vectors and the greedy tokens -> out_dir/logits.npy, tokens.npy."""
+    import os
+    weights, _, got, toks = _timed_region_run(quant)
+    del weights
+    np.save(os.path.join(out_dir, "logits.npy"), np.stack(got))
+    np.save(os.path.join(out_dir, "tokens.npy"), np.array(toks, np.int64))
+
+
+@pytest.mark.parametrize("quant", ["f16", "q4_k_m"])
+def test_timed_region_full_depth_against_the_oracle(quant, tmp_path):
+    """the benchmark's own timed region against the oracle at full depth — the whole Llama-3.2-3B (28 blocks,
+    V = 128256), a 512-token prompt through the MFMA prefill, then 8 greedy tokens on the decode path (positions 512..519), against
+    `OracleLlama` fed the same 520 tokens one by one in fp32 (the reference's loop, LlamaModel.cs:103-126; ~60 s on 16 host
+    threads).  The prefill rounds its GEMM operands to fp16, so the bar is the stated fp16 tolerance on the logits
+    (2e-2 * max(1, max|logit|), about 1e-1 absolute here) with identical greedy tokens at every step; the oracle skips the lm_head for the prompt.
+    Also as Q4_K_M (bench.py --quant q4_k_m: the oracle multiplies the dequantised weights), in both prefill forms: the default one
+    that widens each block's K-quant matrices to fp16 for the direct-to-LDS GEMMs (in this process) and the dequant-in-LDS GEMMs of
+    NFAI_PREFILL_FUSED=1 (read once per process: a child process, running while this one computes the one oracle pass)."""
+    import os
+    import subprocess
+    import sys
+    import bench as B
+    dims = synth.LLAMA_32_3B
+    T, G = 512, 8
+    C = T + G + 1
+    weights, prompt, got, toks = _timed_region_run(quant, T, G)
+    forms = {"default": (got, toks)}
+    child = None
+    if quant != "f16":
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+        env["NFAI_PREFILL_FUSED"] = "1"
+        code = (f"import sys; sys.path[:0] = [{root!r}, {os.path.join(root, 'tests')!r}]; import test_gpu_model as t; "
+                f"t._timed_region_child({quant!r}, {str(tmp_path)!r})")
+        child = subprocess.Popen([sys.executable, "-c", code], env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    try:
+        ref = orc.OracleLlama(odesc(dims, C), B.host_weights(weights))
+        del weights
+        for t in prompt[:-1]:
+            ref.step(int(t), want_logits=False)
+        wants = [ref.step(int(prompt[-1]))]
+        for i in range(G):
+            wants.append(ref.step(toks[i]))
+    finally:
+        if child is not None:
+            try:
+                out, _ = child.communicate(timeout=900)
+            except subprocess.TimeoutExpired:
+                child.kill()
+                out = child.communicate()[0] + "\n(child killed at its 900 s limit)"
+    if child is not None:
+        assert child.returncode == 0, out[-4000:]
+        forms["fused"] = (list(np.load(tmp_path / "logits.npy")), np.load(tmp_path / "tokens.npy").tolist())
+    for form, (got, toks) in forms.items():
+        worst = 0.0
+        for i in range(G + 1):
+            want = wants[i]
+            err, scale = float(np.abs(got[i] - want).max()), max(1.0, float(np.abs(want).max()))
+            worst = max(worst, err / scale)
+            top2 = np.sort(want)[-2:]
+            assert err <= 2e-2 * scale, (form, i, err, scale)
+            assert orc.argmax(want) == toks[i], (form, i, orc.argmax(want), toks[i], "oracle top-1 / top-2 margin", float(top2[1] - top2[0]))
+        print(f"full-depth timed region ({quant}, {form} prefill): worst max|dlogit| / max(1, max|logit|) over {G + 1} positions = {worst:.3g}")
 
 
 @pytest.mark.parametrize("dims", [synth.LLAMA_32_3B, synth.LLAMA_32_1B], ids=lambda d: d.name)
@@ -780,3 +830,112 @@ def test_decode_is_bit_reproducible(mgr, dims):
         assert np.array_equal(m2.Step(int(t))[0], first[i]), i
     m.Dispose()
     m2.Dispose()
+
+
+def test_chunked_ingest_full_width_and_depth():
+    """RunAsync's prompt sequence on the whole Llama-3.2-1B (16 blocks, fp16, V = 128256): a model with max_batch = 256 ingests the
+    first 699 tokens of a 700-token prompt (nfai_hip_llama_ingest: chunks of 256, 256 and a ragged 187, the second and third
+    attending across the K / V rows the earlier ones cached), steps the last prompt token, then 8 greedy tokens — against
+    `OracleLlama` fed all 708 tokens one by one.  Logits of the 9 sampled steps within the stated fp16 bar (2e-2 * max(1,
+    max|logit|)) with identical greedy tokens; K and V rows on both sides of the chunk edges and of the last prompt token, first
+    and last layer, within the 2e-2 of test_prefill_mfma_matches_token_by_token."""
+    import torch
+    import bench as B
+    from nfai_amd import _lib
+    from nfai_amd.hip import HipBufferManager
+    from nfai_amd.llama_model import LlamaModel
+    dims = synth.LLAMA_32_1B
+    torch.cuda.set_device(0)
+    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant="f16", seed=4321)
+    n, G = 700, 8
+    C = n + G + 4
+    mgr = HipBufferManager(0)
+    m = LlamaModel(mgr, synth.make_metadata(dims), B.as_model_tensors(_lib, weights), C, max_batch=256,
+                   dims=dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0))
+    prompt = synth.make_tokens(dims, n, seed=23)
+    prompt[0] = 128000
+    m.Ingest(prompt[:-1])
+    assert m.Pos == n - 1
+    got, toks = [], []
+    tok = int(prompt[-1])
+    for _ in range(G + 1):
+        lg, tok = m.Step(tok)
+        got.append(lg)
+        toks.append(tok)
+    assert m.Pos == n + G
+    rows = (255, 256, 511, 512, n - 2)
+    kv = {(l, v, p): m.ReadKV(l, v, p) for l in (0, dims.L - 1) for v in (False, True) for p in rows}
+    m.Dispose()
+    mgr.Dispose()
+    ref = orc.OracleLlama(odesc(dims, C), B.host_weights(weights))
+    del weights
+    for t in prompt[:-1]:
+        ref.step(int(t), want_logits=False)
+    worst = 0.0
+    for i, want in enumerate([ref.step(int(prompt[-1]))] + [None] * G):
+        if want is None:
+            want = ref.step(toks[i - 1])
+        err, scale = float(np.abs(got[i] - want).max()), max(1.0, float(np.abs(want).max()))
+        worst = max(worst, err / scale)
+        top2 = np.sort(want)[-2:]
+        assert err <= 2e-2 * scale, (i, err, scale)
+        assert orc.argmax(want) == toks[i], (i, orc.argmax(want), toks[i], "oracle top-1 / top-2 margin", float(top2[1] - top2[0]))
+    for (l, v, p), row in kv.items():
+        np.testing.assert_allclose(row, (ref.vcache(l) if v else ref.kcache(l))[p], rtol=0, atol=2e-2, err_msg=f"layer {l} {'V' if v else 'K'} row {p}")
+    print(f"chunked ingest (1B, 256-row chunks): worst max|dlogit| / max(1, max|logit|) over {G + 1} positions = {worst:.3g}")
+
+
+def _xcd_lib():
+    import ctypes as C
+    from nfai_amd import _lib
+    lib = _lib.load()
+    lib.nfai_hip_debug_xcd_shares.argtypes = [_lib.H, C.POINTER(C.c_uint16)]
+    lib.nfai_hip_debug_xcd_shares.restype = C.c_int32
+    lib.nfai_hip_debug_gemv_dealt.argtypes = []
+    lib.nfai_hip_debug_gemv_dealt.restype = C.c_uint64
+    return lib
+
+
+def test_lm_head_dealt_by_forced_shares_at_model_level():
+    """The model's lm_head + ArgMax launch with its rows dealt by a forced, skewed share vector (nfai_hip_debug_xcd_shares before
+    the model is finalised: the token graph captures the shares), whatever the box's own probe would pick: two blocks at the 3B
+    widths with the full 128256-row vocabulary.  A twin on a context with dealing off must give bit-identical logits at 16
+    positions and the same greedy tokens (the device loop), both within the end-to-end tolerance of the oracle."""
+    import ctypes as C
+    from dataclasses import replace
+    from nfai_amd.hip import HipBufferManager
+    from nfai_amd.llama_model import LlamaModel
+    lib = _xcd_lib()
+    skewed = (30, 50, 41, 40, 40, 40, 40, 39)
+    d2 = replace(synth.LLAMA_32_3B, L=2, name="llama-3.2-3b-2blk-full-vocab")
+    w = synth.make_weights(d2, seed=43)
+    N, n_ctx = 16, 2 * 16 + 4
+    mo, md = HipBufferManager(0), HipBufferManager(0)
+    assert lib.nfai_hip_debug_xcd_shares(mo.handle, None) == 0
+    assert lib.nfai_hip_debug_xcd_shares(md.handle, (C.c_uint16 * 8)(*skewed)) == 0
+    assert mo.XcdShares()[0] == [0] * 8 and md.XcdShares()[0] == list(skewed)
+    c0 = lib.nfai_hip_debug_gemv_dealt()
+    off = LlamaModel(mo, synth.make_metadata(d2), w, n_ctx)
+    g_off = off.Greedy(5, N)
+    assert lib.nfai_hip_debug_gemv_dealt() == c0, "a context with dealing off dealt"
+    dealt = LlamaModel(md, synth.make_metadata(d2), w, n_ctx)
+    g_dealt = dealt.Greedy(5, N)
+    assert lib.nfai_hip_debug_gemv_dealt() > c0, "the lm_head of the forced context did not take the XD path"
+    ref = orc.OracleLlama(odesc(d2, n_ctx), w)
+    tok, want_toks, wants = 5, [], []
+    for _ in range(N):
+        wants.append(ref.step(tok))
+        tok = orc.argmax(wants[-1])
+        want_toks.append(tok)
+    assert g_dealt.tolist() == g_off.tolist() == want_toks
+    off.Reset()
+    dealt.Reset()
+    for i, t in enumerate([5] + want_toks[:-1]):
+        la, aa = off.Step(t)
+        lb, ab = dealt.Step(t)
+        assert np.array_equal(la, lb) and aa == ab, (i, np.flatnonzero(~(la == lb))[:16])
+        assert np.abs(lb - wants[i]).max() <= logit_tol(wants[i]), (i, np.abs(lb - wants[i]).max())
+    off.Dispose()
+    dealt.Dispose()
+    mo.Dispose()
+    md.Dispose()

@@ -760,3 +760,156 @@ def test_engine_block_op_level(mgr, E, F, H, Hkv, D, with_qkv):
     xo2, sc2 = run()  # second call: epoch 2, same values bit for bit
     np.testing.assert_array_equal(xo, xo2)
     assert (sc2[: (E + F) * 2].reshape(-1, 2)[:, 1] == 2).all()
+
+
+# ---- rows dealt to the XCDs by share (the XD instantiations of k_gemv) -----------------------------------------------------------
+# The model's lm_head (and gate | up, when a shape passes the gate of launch_gemv) deals its unit groups to the eight blockIdx % 8
+# labels by the shares gemv_xcd_calibrate measured; which shares, and whether a launch deals at all, depends on the box.  The
+# test hook nfai_hip_debug_xcd_shares forces the shares of a context (for the op-level entries too), and nfai_hip_debug_gemv_dealt
+# counts the launches that took the XD instantiations, so a case cannot pass on the plain path unnoticed.
+XD_DEALT = {
+    "skewed": (30, 50, 41, 40, 40, 40, 40, 39),          # S = 320
+    "one-at-1": (1, 40, 40, 40, 40, 40, 40, 40),         # S = 281
+    "one-at-1024": (40, 40, 40, 1024, 40, 40, 40, 40),   # S = 1304: labels 4..7 sit behind the 1024 in every round
+    "largest": (1024,) * 7 + (1023,),                    # S = 8191: all eight at 1024 would be uniform (next table)
+}
+XD_PLAIN = {                                             # refused by the launch: the plain dealing, bit-identical, not counted
+    "uniform": (40,) * 8,
+    "uniform-1024": (1024,) * 8,
+    "zero": (0, 40, 40, 40, 40, 40, 40, 40),
+    "1025": (40, 40, 40, 40, 1025, 40, 40, 40),
+}
+
+
+def _xcd_lib():
+    import ctypes as C
+    from nfai_amd import _lib
+    lib = _lib.load()
+    lib.nfai_hip_debug_xcd_shares.argtypes = [_lib.H, C.POINTER(C.c_uint16)]
+    lib.nfai_hip_debug_xcd_shares.restype = C.c_int32
+    lib.nfai_hip_debug_gemv_dealt.argtypes = []
+    lib.nfai_hip_debug_gemv_dealt.restype = C.c_uint64
+    return lib
+
+
+def _force_shares(m, shares):
+    """Deal the GEMV rows of context `m` by `shares` (None: dealing off)."""
+    import ctypes as C
+    arr = None if shares is None else (C.c_uint16 * 8)(*shares)
+    assert _xcd_lib().nfai_hip_debug_xcd_shares(m.handle, arr) == 0
+
+
+def _xd_launches(m, launch, out, n):
+    """{name: (outputs, counter advance)} of `launch()` on context m: dealing off first, then every forced share vector; `out` is
+    poisoned with NaN before every launch, so a row no wave wrote stays visible."""
+    lib = _xcd_lib()
+    res = {}
+    for name, shares in [("off", None)] + list(XD_DEALT.items()) + list(XD_PLAIN.items()):
+        _force_shares(m, shares)
+        out.SetValue(np.full(n, np.nan, np.float32))
+        c0 = lib.nfai_hip_debug_gemv_dealt()
+        idx = launch()
+        res[name] = (out.GetValue().copy(), idx, int(lib.nfai_hip_debug_gemv_dealt() - c0))
+    return res
+
+
+def _check_xd(res):
+    off = res["off"]
+    assert off[2] == 0 and np.isfinite(off[0]).all()
+    for name in XD_DEALT:
+        y, idx, dealt = res[name]
+        assert dealt == 1, (name, "the launch did not take the XD path")
+        assert np.array_equal(y, off[0]) and idx == off[1], (name, np.flatnonzero(~(y == off[0]))[:16])
+    for name in XD_PLAIN:
+        y, idx, dealt = res[name]
+        assert dealt == 0, (name, "shares the launch must refuse were dealt")
+        assert np.array_equal(y, off[0]) and idx == off[1], name
+
+
+def _gemv_ref_tiled(W, x, tile=8192):
+    """orc.gemv_f16w and gemv_tol over the whole table, a tile of rows at a time (the fp64 |W| |x| of a 128256-row table at once
+    would not fit comfortably)."""
+    ref, tol = np.empty(W.shape[0], np.float32), np.empty(W.shape[0])
+    for r0 in range(0, W.shape[0], tile):
+        Wt = W[r0:r0 + tile]
+        ref[r0:r0 + tile] = orc.gemv_f16w(Wt, x)
+        tol[r0:r0 + tile] = gemv_tol(Wt, x)
+    return ref, tol
+
+
+@pytest.mark.parametrize("V,E,norm,row0", [(128256, 2048, True, True), (128256, 2048, False, False), (128256, 3072, True, False),
+                                           (128256, 3072, False, True), (128256, 4096, True, True), (128256, 4096, False, False),
+                                           (128257, 3072, True, False), (99991, 2048, False, True)])
+def test_lmhead_argmax_xcd_dealt(V, E, norm, row0):
+    """The fused lm_head + ArgMax launch with its rows dealt by forced shares, at the vocabulary of the Llama 3 models (V = 128257
+    and the prime 99991: the last unit group is partial).  The shares cover skewed rounds, a label at 1, one at 1024 ahead of four
+    others, the largest round the launch takes (S = 8191), and rounds whose ragged last one (total_groups % S) ends before some
+    labels' offset.  Every one of the V logits against the oracle, all of them and the index bit-identical to the same launch with
+    dealing off; uniform and out-of-range shares (0, 1025) must give the plain dealing.  Eight rows are copies of the winning row,
+    spread from the first (or row 77) through the last dealing round to the last row: the index is the first copy."""
+    from nfai_amd.hip import HipBufferManager, ShaderProperty
+    from nfai_amd._lib import call
+    r = rng(V * 3 + E)
+    base = (0.02 * r.standard_normal((4093, E))).astype(np.float16)   # a prime period: no tile lines up with a dealing round
+    W = np.tile(base, ((V + 4092) // 4093, 1))[:V].copy()
+    W[:, :8] = (0.02 * r.standard_normal((V, 8))).astype(np.float16)   # and every row differs
+    x = r.standard_normal(E).astype(np.float32)
+    g = (1 + 0.1 * r.standard_normal(E)).astype(np.float32)
+    xn = orc.rmsnorm(x, g, 1e-5) if norm else x
+    copies = [0 if row0 else 77, V // 3, V // 2 + 3, 2 * V // 3, V - 101, V - 37, V - 2, V - 1]
+    W[copies] = (np.sign(xn) * 0.05).astype(np.float16)
+    ref, tol = _gemv_ref_tiled(W, xn)
+    m = HipBufferManager(0)
+    try:
+        tab = m.UploadWeight(1, W, V, E)
+        px, pg, pl, pi = ShaderProperty(m, E), ShaderProperty(m, E), ShaderProperty(m, V), ShaderProperty(m, 1, np.uint32)
+        px.SetValue(x)
+        pg.SetValue(g)
+
+        def launch():
+            call("nfai_hip_lmhead_argmax", m.handle, tab.handle, 1, px.handle, pg.handle if norm else 0, 1e-5, pl.handle, pi.handle, V, E)
+            return int(pi.GetValue()[0])
+
+        res = _xd_launches(m, launch, pl, V)
+        _check_xd(res)
+        lg, idx, _ = res["off"]
+        bad = np.flatnonzero(~(np.abs(lg - ref) <= tol))
+        assert bad.size == 0, (bad[:16], lg[bad[:4]], ref[bad[:4]])
+        assert idx == copies[0] == orc.argmax(lg), (idx, copies[0])
+    finally:
+        m.Dispose()
+
+
+@pytest.mark.parametrize("E,F,norm", [(2048, 16384, True), (2048, 16384, False), (1536, 20000, True)])
+def test_gemv_gateup_silu_xcd_dealt(E, F, norm):
+    """gate | up with its rows dealt by forced shares.  No model width deals this launch today (at the Llama widths it has 2-4 unit
+    groups per wave, below the >= 8 the launch asks for), so the shapes are synthetic: F = 16384 and 20000 rows at one unit per
+    group give exactly and a little over 8 groups per wave of the 512-workgroup grid.  Against the oracle's silu(gate) * up, and
+    bit-identical to dealing off under every share vector of test_lmhead_argmax_xcd_dealt."""
+    from nfai_amd import _lib
+    from nfai_amd._lib import call
+    from nfai_amd.hip import HipBufferManager, ShaderProperty
+    r = rng(E + F + norm)
+    Wg = (0.02 * r.standard_normal((F, E))).astype(np.float16)
+    Wu = (0.02 * r.standard_normal((F, E))).astype(np.float16)
+    x = r.standard_normal(E).astype(np.float32)
+    g = (1 + 0.1 * r.standard_normal(E)).astype(np.float32)
+    xn = orc.rmsnorm(x, g, 1e-5) if norm else x
+    want = orc.mul(orc.gemv_f16w(Wu, xn), orc.silu(orc.gemv_f16w(Wg, xn)))
+    m = HipBufferManager(0)
+    try:
+        pg_, pu = m.UploadWeight(_lib.F16, Wg, F, E), m.UploadWeight(_lib.F16, Wu, F, E)
+        px, pg, py = ShaderProperty(m, E), ShaderProperty(m, E), ShaderProperty(m, F)
+        px.SetValue(x)
+        pg.SetValue(g)
+
+        def launch():
+            call("nfai_hip_gemv_gateup_silu", m.handle, pg_.handle, pu.handle, _lib.F16, px.handle, pg.handle if norm else 0, 1e-5,
+                 py.handle, F, E)
+            return 0
+
+        res = _xd_launches(m, launch, py, F)
+        _check_xd(res)
+        np.testing.assert_allclose(res["off"][0], want, rtol=2e-5, atol=1e-5)
+    finally:
+        m.Dispose()
