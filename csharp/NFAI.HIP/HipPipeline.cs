@@ -56,6 +56,16 @@ public sealed unsafe class HipPipeline : IDisposable
     public void Abort() => Native.Check(Native.nfai_hip_pp_abort(handle));
     public void BroadcastToken(nint tokenDev, uint root) => Native.Check(Native.nfai_hip_pp_bcast_token(handle, (void*)tokenDev, root));
 
+    /// <summary>The prompt phase of this rank's stage for one chunk of n prompt tokens (nfai_hip_llama_stage_ingest; the reference's
+    /// prompt loop LlamaModel.cs:103-126 sliced by the stage's blocks).  Rank 0 passes the chunk's tokens; later ranks the device rows
+    /// [n][n_embd] received from rank - 1; every rank but the last a device buffer of [n][n_embd] floats it then sends to rank + 1
+    /// (SendHidden with n * n_embd floats, in the same tick as the peer's RecvHidden).  Stream-ordered; only rank 0 blocks.</summary>
+    public static void StageIngest(ulong model, ReadOnlySpan<uint> tokens, nint hiddenInDev, nint hiddenOutDev, uint n)
+    {
+        fixed (uint* t = tokens)
+            Native.Check(Native.nfai_hip_llama_stage_ingest(model, tokens.IsEmpty ? null : t, (void*)hiddenInDev, (void*)hiddenOutDev, n));
+    }
+
     public void Dispose()
     {
         if (handle == 0) return;

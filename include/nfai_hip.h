@@ -291,6 +291,24 @@ int32_t nfai_hip_llama_ingest(nfai_model_t model, const uint32_t *tokens, uint32
 #define NFAI_TOKEN_ON_DEVICE 0xFFFFFFFFu /* stage_step: use the token word already in device memory */
 int32_t nfai_hip_llama_stage_step(nfai_model_t model, uint32_t token, const void *hidden_in_dev,
                                   void *hidden_out_dev, float *logits_host, uint32_t *argmax);
+/* The prompt phase of ONE pipeline stage (LlamaModel.cs:103-126 feeds the prompt token by token through every block; a stage runs
+ * the blocks [layer_begin, layer_end) of that loop, :118-121): n prompt tokens at positions pos..pos+n-1 leave their K / V rows in
+ * this stage's cache; nothing is sampled, no logits are formed.  The stage's position advances by n: the next _stage_step (the last
+ * prompt token, whose output IS sampled, :128-130) continues from there.
+ * First stage: `tokens` (host, n entries) are embedded, hidden_in_dev must be NULL.  Other stages: hidden_in_dev = [n][n_embd] fp32
+ * (device), tokens must be NULL.  Non-last stage: hidden_out_dev = [n][n_embd] fp32 (device) receives the stage's output rows,
+ * which the next stage takes as its hidden_in.  Last stage: hidden_out_dev must be NULL.
+ * Engine: with a prefill workspace (desc.max_batch > 0) and the MFMA rules of _ingest (the token-embedding rule on the first stage
+ * only), the MFMA prefill in chunks of max_batch rows (same precision as _ingest); otherwise n times the body of _stage_step, row i
+ * in -> row i out, bit-identical to n _stage_step calls.  A model that is first AND last stage: exactly nfai_hip_llama_ingest.
+ * Ordering: enqueued on the context stream, in order with _stage_step and nfai_hip_pp_*; a non-first stage does not block and makes
+ * no host round trip.  The first stage blocks until the copies out of the caller's (pageable) `tokens` have run.
+ * K-quant stages: the first call widens the stage's matrices to fp16 as _prefill does (2 bytes per weight of the stage's blocks,
+ * kept); slots made with _share_tensors on the same context reuse the donor's copy — one copy per stage, not one per slot.
+ * Errors, returned before anything is enqueued: NFAI_ERR_KV_FULL when pos + n exceeds the capacity, NFAI_ERR_INVALID for a token
+ * >= V or a missing / superfluous pointer for this stage's role.  n == 0 is a no-op. */
+int32_t nfai_hip_llama_stage_ingest(nfai_model_t model, const uint32_t *tokens, const void *hidden_in_dev,
+                                    void *hidden_out_dev, uint32_t n);
 /* 4-byte device-to-device copies of the model's token word (the last stage's argmax / the first
  * stage's next input), stream-ordered: lets RCCL carry the token between pipeline ends with no
  * host round trip (the reference reads V logits back and samples on the host, LlamaModel.cs:128-130). */

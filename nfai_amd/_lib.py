@@ -103,6 +103,7 @@ SIGNATURES = {
     "nfai_hip_llama_prefill": [H, C.POINTER(u32), u32, C.POINTER(f32)],
     "nfai_hip_llama_ingest": [H, C.POINTER(u32), u32],
     "nfai_hip_llama_stage_step": [H, u32, vp, vp, C.POINTER(f32), C.POINTER(u32)],
+    "nfai_hip_llama_stage_ingest": [H, C.POINTER(u32), vp, vp, u32],
     "nfai_hip_llama_token_to_device": [H, vp],
     "nfai_hip_llama_token_from_device": [H, vp],
     "nfai_hip_llama_reset": [H],

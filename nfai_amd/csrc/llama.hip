@@ -15,6 +15,7 @@
 #include <functional>
 
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -35,6 +36,19 @@ struct Tensor {
 struct Layer {
     Tensor attn_norm, wq, wk, wv, wo, ffn_norm, wgate, wup, wdown;
     void *kcache = nullptr, *vcache = nullptr;
+};
+
+// K-quant models: the blocks' matrices widened to fp16 for the MFMA GEMMs (allocated on first use) — one slot per block, each
+// widened ONCE and kept, when that fits the memory budget (288 GB of HBM: 6.4 GB at 3B, 16 GB at 8B); otherwise one slot, re-widened
+// for every block of every chunk.  Shared by the slots of a pipeline stage (nfai_hip_llama_share_tensors on the same context): one
+// copy per set of weights, not one per in-flight sequence.
+struct WideShadow {
+    void *ptr = nullptr;
+    uint64_t bytes = 0;
+    bool all = false;
+    uint64_t slot = 0;               // bytes per block slot
+    std::vector<uint8_t> done;       // per block: slot holds the current weights
+    ~WideShadow() { if (ptr) hipFree(ptr); }
 };
 
 enum KClass { KC_QKV = 0, KC_ATTN = 1, KC_WO = 2, KC_GATEUP = 3, KC_DOWN = 4, KC_LMHEAD = 5, KC_OTHER = 6, KC_ENGINE = 7, KC_N = 8 };
@@ -77,11 +91,7 @@ struct Model {
         float *CS = nullptr;       // cos / sin of the chunk's positions [T][D/2][2] (the q | k | v epilogue)
         float *X = nullptr, *H1 = nullptr, *Q = nullptr, *K = nullptr, *V = nullptr, *ATT = nullptr, *G = nullptr, *U = nullptr, *SC = nullptr;
         void *XN = nullptr, *QH = nullptr, *KH = nullptr, *VT = nullptr, *P = nullptr, *ACT = nullptr;  // fp16
-        void *WF16 = nullptr;      // K-quant models: the blocks' matrices widened to fp16 for the MFMA GEMMs (allocated on first use) —
-        uint64_t wf16_bytes = 0;   // one slot per block, each widened ONCE and kept, when that fits the memory budget (288 GB of HBM: 6.4 GB
-        bool wf16_all = false;     // at 3B, 16 GB at 8B); otherwise one slot, re-widened for every block of every chunk
-        uint64_t wf16_slot = 0;    // bytes per block slot
-        std::vector<uint8_t> wf16_done;  // per block: slot holds the current weights
+        std::shared_ptr<WideShadow> wide = std::make_shared<WideShadow>();
     } pf;
     uint32_t pos_host = 0;
     const float *x_last = nullptr;   // where the last enqueued token left the hidden state (m->x, or m->h on the engine path)
@@ -813,7 +823,7 @@ NFAI_API int32_t nfai_hip_llama_destroy(nfai_model_t h)
                     m->q, m->att, m->act, m->logits, m->xn, m->qraw, m->scores, m->wts, m->proj, m->gate, m->up};
     for (void *p : ptrs) if (p) hipFree(p);
     void *pfp[] = {m->pf.CS, m->pf.toks, m->pf.X, m->pf.H1, m->pf.Q, m->pf.K, m->pf.V, m->pf.ATT, m->pf.G, m->pf.U, m->pf.SC,
-                   m->pf.XN, m->pf.QH, m->pf.KH, m->pf.VT, m->pf.P, m->pf.ACT, m->pf.WF16};
+                   m->pf.XN, m->pf.QH, m->pf.KH, m->pf.VT, m->pf.P, m->pf.ACT};
     for (void *p : pfp) if (p) hipFree(p);
     if (m->h_pin) hipHostFree(m->h_pin);
     m->magic = 0;
@@ -874,7 +884,9 @@ static int set_tensor_impl(Model *m, const char *name, int type, uint64_t rows, 
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return fail_free(nt.ptr, nullptr, fail(NFAI_ERR_HIP, "set_tensor(%s): upload failed: %s", name, hipGetErrorString(e)));
     }
-    std::fill(m->pf.wf16_done.begin(), m->pf.wf16_done.end(), 0);  // the kept fp16 copies of the K-quant prefill are of the old weights
+    // the kept fp16 copies of the K-quant prefill are of the old weights; a copy other slots still read stays theirs
+    if (m->pf.wide.use_count() > 1) m->pf.wide = std::make_shared<WideShadow>();
+    else std::fill(m->pf.wide->done.begin(), m->pf.wide->done.end(), 0);
     m->finalized = false;  // graphs captured over the old pointer are dropped by the next finalize
     if (t->owned && t->ptr) {
         hipStreamSynchronize(s);  // nothing enqueued may still read the old storage
@@ -910,7 +922,9 @@ NFAI_API int32_t nfai_hip_llama_share_tensors(nfai_model_t h, nfai_model_t donor
         share(L.attn_norm, S.attn_norm); share(L.wq, S.wq); share(L.wk, S.wk); share(L.wv, S.wv); share(L.wo, S.wo);
         share(L.ffn_norm, S.ffn_norm); share(L.wgate, S.wgate); share(L.wup, S.wup); share(L.wdown, S.wdown);
     }
-    std::fill(m->pf.wf16_done.begin(), m->pf.wf16_done.end(), 0);
+    // the donor's fp16 copies of the K-quant matrices too (prefill, stage ingest): same weights, same stream, so a slot finds them
+    // widened by whichever model ran first, in stream order.  Another context's stream would race the re-widened single slot.
+    m->pf.wide = src->ctx == m->ctx ? src->pf.wide : std::make_shared<WideShadow>();
     m->finalized = false;
     return NFAI_OK;
 }
@@ -1130,8 +1144,11 @@ NFAI_API int32_t nfai_hip_llama_decode_greedy(nfai_model_t h, uint32_t first_tok
     return nfai_hip_llama_fetch_tokens(h, n_steps, tokens_out);
 }
 
-// One chunk of T prompt tokens through every block on the MFMA path (kernels_prefill.hip).
-static int prefill_chunk(Model *m, const uint32_t *tokens, uint32_t T)
+// One chunk of T prompt tokens through every block on the MFMA path (kernels_prefill.hip).  A pipeline stage (nfai_hip_llama_stage_ingest)
+// passes hidden_in ([T][E] fp32, device: the previous stage's rows) in place of tokens, and hidden_out ([T][E]) to take this stage's
+// output rows; `stage` sets the position word from the stream (no pageable host source behind it).
+static int prefill_chunk(Model *m, const uint32_t *tokens, uint32_t T, const float *hidden_in = nullptr, float *hidden_out = nullptr,
+                         bool stage = false)
 {
     const nfai_llama_desc &d = m->d;
     Model::Prefill &w = m->pf;
@@ -1263,11 +1280,15 @@ static int prefill_chunk(Model *m, const uint32_t *tokens, uint32_t T)
         ra_used = true;
         return NFAI_OK;
     };
-    HIP_TRY(hipMemcpyAsync(w.toks, tokens, (size_t)T * 4, hipMemcpyHostToDevice, s));
-    if (is_kquant(m->token_embd.type))
-        P_TRY(launch_embed_rows_kqt(m->token_embd.ptr, m->token_embd.type, m->token_embd.rows, w.toks, w.X, T, d.E, s));
-    else
-        P_TRY(launch_embed_rows(m->token_embd.ptr, m->token_embd.type, w.toks, w.X, T, d.E, s));
+    if (hidden_in) {   // a later pipeline stage: the previous stage's output rows are this chunk's hidden state
+        HIP_TRY(hipMemcpyAsync(w.X, hidden_in, (size_t)T * d.E * 4, hipMemcpyDeviceToDevice, s));
+    } else {
+        HIP_TRY(hipMemcpyAsync(w.toks, tokens, (size_t)T * 4, hipMemcpyHostToDevice, s));
+        if (is_kquant(m->token_embd.type))
+            P_TRY(launch_embed_rows_kqt(m->token_embd.ptr, m->token_embd.type, m->token_embd.rows, w.toks, w.X, T, d.E, s));
+        else
+            P_TRY(launch_embed_rows(m->token_embd.ptr, m->token_embd.type, w.toks, w.X, T, d.E, s));
+    }
     // RoPE and the q / KV-cache stores in the q | k | v GEMM's epilogue (fp16 weights, also widened ones); NFAI_PREFILL_ROPE_FUSED=0:
     // GEMM -> fp32 q | k | v -> k_rope_store_tiles (bit-identical results, one launch and a 10 MB round trip more per block)
     const char *env_rf = getenv("NFAI_PREFILL_ROPE_FUSED");
@@ -1275,21 +1296,22 @@ static int prefill_chunk(Model *m, const uint32_t *tokens, uint32_t T)
     if (rope_fused_ok) P_TRY(launch_rope_table(m->d_freqs, pos0, T, d.D, d.rope_dims, w.CS, s));
     for (Layer &Lq : m->layers) {
         Layer L = Lq;
-        if (widen && w.WF16) {
+        WideShadow &wd = *w.wide;
+        if (widen && wd.ptr) {
             const size_t li = (size_t)(&Lq - m->layers.data());
-            const bool kept = w.wf16_all && w.wf16_done[li];  // widened by an earlier chunk / prefill and still current
-            uint64_t off = w.wf16_all ? li * w.wf16_slot : 0;
-            const uint64_t end = off + w.wf16_slot;
+            const bool kept = wd.all && wd.done[li];  // widened by an earlier chunk / prefill and still current
+            uint64_t off = wd.all ? li * wd.slot : 0;
+            const uint64_t end = off + wd.slot;
             for (Tensor *tq : {&L.wq, &L.wk, &L.wv, &L.wo, &L.wgate, &L.wup, &L.wdown}) {
                 if (tq->type == NFAI_F16) continue;
                 const uint64_t bytes = tq->rows * tq->cols * 2;
                 if (off + bytes > end) return fail(NFAI_ERR_STATE, "prefill: fp16 weight scratch too small");
-                void *dst = static_cast<uint8_t *>(w.WF16) + off;
+                void *dst = static_cast<uint8_t *>(wd.ptr) + off;
                 if (!kept) P_TRY(launch_dequant_t16_f16(tq->ptr, tq->type, tq->rows, tq->cols, dst, s));
                 tq->ptr = dst; tq->type = NFAI_F16; tq->owned = false;
                 off += (bytes + 255) / 256 * 256;
             }
-            if (w.wf16_all) w.wf16_done[li] = 1;
+            if (wd.all) wd.done[li] = 1;
         }
         if (pend_ks) {   // the previous block's Wdown left residual + K-split slabs: combine -> w.X and normalise in one pass
             P_TRY(launch_rmsnorm_rows_combine(w.SC, pend_ks, pend_R, w.X, static_cast<const float *>(L.attn_norm.ptr), w.XN, T, d.E, d.eps, s));
@@ -1380,26 +1402,64 @@ static int prefill_chunk(Model *m, const uint32_t *tokens, uint32_t T)
         HIP_TRY(hipStreamWaitEvent(s, ev, 0));
     }
 #undef P_TRY
+    // a non-last pipeline stage: its output rows (after the tail combine above) are the next stage's input
+    if (hidden_out) HIP_TRY(hipMemcpyAsync(hidden_out, w.X, (size_t)T * d.E * 4, hipMemcpyDeviceToDevice, s));
     // the last token's hidden state continues on the M = 1 path (output norm + lm_head + argmax)
     HIP_TRY(hipMemcpyAsync(m->x, w.X + (size_t)(T - 1) * d.E, (size_t)d.E * 4, hipMemcpyDeviceToDevice, s));
     const uint32_t newpos = pos0 + T;
-    HIP_TRY(hipMemcpyAsync(m->d_pos, &newpos, 4, hipMemcpyHostToDevice, s));
+    if (stage)
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m->d_pos), (int)newpos, 1, s));
+    else
+        HIP_TRY(hipMemcpyAsync(m->d_pos, &newpos, 4, hipMemcpyHostToDevice, s));
     m->pos_host = newpos;
     m->x_last = m->x;
     return NFAI_OK;
 }
 
-static bool prefill_mfma_ok(const Model *m)
+// The MFMA prefill's type and shape rules for this model's blocks; the token embedding is read only where the prompt enters (embeds).
+static bool prefill_mfma_rules(const Model *m, bool embeds)
 {
-    if (m->pf.T == 0 || m->unfused || !(m->first_stage && m->last_stage)) return false;
+    if (m->pf.T == 0 || m->unfused) return false;
     const nfai_llama_desc &d = m->d;
     if (d.E % 64 || d.F % 64 || (d.H * d.D) % 64 || (d.Hkv * d.D) % 64) return false;
     const int et = m->token_embd.type;
-    if (et != NFAI_F16 && et != NFAI_F32 && et != NFAI_Q4_K_T16 && et != NFAI_Q6_K_T16) return false;
+    if (embeds && et != NFAI_F16 && et != NFAI_F32 && et != NFAI_Q4_K_T16 && et != NFAI_Q6_K_T16) return false;
     for (const Layer &L : m->layers)
         for (const Tensor *t : {&L.wq, &L.wk, &L.wv, &L.wo, &L.wgate, &L.wup, &L.wdown})
             if (t->type != NFAI_F16 && t->type != NFAI_Q4_K_T16 && t->type != NFAI_Q6_K_T16) return false;
     return true;
+}
+
+static bool prefill_mfma_ok(const Model *m) { return m->first_stage && m->last_stage && prefill_mfma_rules(m, true); }
+
+// The fp16 copies of a K-quant model's matrices (WideShadow), allocated at the first prefill of any model that shares them.
+static int ensure_wide_shadow(Model *m)
+{
+    WideShadow &wd = *m->pf.wide;
+    if (wd.ptr || (getenv("NFAI_PREFILL_FUSED") && atoi(getenv("NFAI_PREFILL_FUSED")))) return NFAI_OK;
+    uint64_t need = 0;
+    for (const Layer &L : m->layers) {
+        uint64_t b = 0;
+        for (const Tensor *t : {&L.wq, &L.wk, &L.wv, &L.wo, &L.wgate, &L.wup, &L.wdown})
+            if (t->type != NFAI_F16) b += (t->rows * t->cols * 2 + 255) / 256 * 256;
+        need = std::max(need, b);
+    }
+    if (!need) return NFAI_OK;
+    // Keep every block's fp16 copy (widened once, at the first prefill) when all of them fit a quarter of the device's memory
+    // and leave 4 GB free: the per-block widening is a quarter of a K-quant prefill (64 us of 230 per block at 3B).  The decode
+    // path never reads these copies.  NFAI_PREFILL_WIDE_ALL=0 / 1 forces one slot / all slots.
+    const uint64_t all = need * m->layers.size();
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const char *env = getenv("NFAI_PREFILL_WIDE_ALL");
+    const bool fits = all + (4ull << 30) <= free_b;
+    const bool want = env ? atoi(env) != 0 : all <= total_b / 4;
+    wd.all = want && fits;
+    wd.slot = need;
+    wd.bytes = wd.all ? all : need;
+    DALLOC(wd.ptr, wd.bytes);
+    wd.done.assign(m->layers.size(), 0);
+    return NFAI_OK;
 }
 
 // head = false: only the KV cache is filled (nfai_hip_llama_ingest: prompt tokens whose output the reference's loop discards).
@@ -1421,31 +1481,7 @@ static int prefill_impl(nfai_model_t h, const uint32_t *tokens, uint32_t n, floa
         return NFAI_OK;
     }
     hipStream_t s = m->ctx->stream;
-    if (!m->pf.WF16 && !(getenv("NFAI_PREFILL_FUSED") && atoi(getenv("NFAI_PREFILL_FUSED")))) {  // fp16 scratch for one block's matrices (K-quant models)
-        uint64_t need = 0;
-        for (const Layer &L : m->layers) {
-            uint64_t b = 0;
-            for (const Tensor *t : {&L.wq, &L.wk, &L.wv, &L.wo, &L.wgate, &L.wup, &L.wdown})
-                if (t->type != NFAI_F16) b += (t->rows * t->cols * 2 + 255) / 256 * 256;
-            need = std::max(need, b);
-        }
-        if (need) {
-            // Keep every block's fp16 copy (widened once, at the first prefill) when all of them fit a quarter of the device's memory
-            // and leave 4 GB free: the per-block widening is a quarter of a K-quant prefill (64 us of 230 per block at 3B).  The decode
-            // path never reads these copies.  NFAI_PREFILL_WIDE_ALL=0 / 1 forces one slot / all slots.
-            const uint64_t all = need * m->layers.size();
-            size_t free_b = 0, total_b = 0;
-            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-            const char *env = getenv("NFAI_PREFILL_WIDE_ALL");
-            const bool fits = all + (4ull << 30) <= free_b;
-            const bool want = env ? atoi(env) != 0 : all <= total_b / 4;
-            m->pf.wf16_all = want && fits;
-            m->pf.wf16_slot = need;
-            m->pf.wf16_bytes = m->pf.wf16_all ? all : need;
-            DALLOC(m->pf.WF16, m->pf.wf16_bytes);
-            m->pf.wf16_done.assign(m->layers.size(), 0);
-        }
-    }
+    S_TRY(ensure_wide_shadow(m));   // fp16 scratch for the blocks' matrices (K-quant models)
     for (uint32_t done = 0; done < n;) {
         const uint32_t T = std::min(n - done, m->d.max_batch);
         int rc = prefill_chunk(m, tokens + done, T);
@@ -1552,6 +1588,54 @@ NFAI_API int32_t nfai_hip_llama_stage_step(nfai_model_t h, uint32_t token, const
         HIP_TRY(hipStreamSynchronize(s));
         if (argmax) *argmax = m->h_pin[0];
     }
+    return NFAI_OK;
+}
+
+// The prompt phase of one pipeline stage (LlamaModel.cs:103-126 sliced by layer_begin / layer_end): n prompt tokens' K / V rows,
+// chunk by chunk on the MFMA prefill, hidden states in and out as [n][E] fp32 device rows.  See include/nfai_hip.h.
+NFAI_API int32_t nfai_hip_llama_stage_ingest(nfai_model_t h, const uint32_t *tokens, const void *hidden_in, void *hidden_out, uint32_t n)
+{
+    MODEL_OR_FAIL(m, h);
+    NEED_FINAL(m);
+    if (n == 0) return NFAI_OK;
+    const nfai_llama_desc &d = m->d;
+    if ((uint64_t)m->pos_host + n > d.C)
+        return fail(NFAI_ERR_KV_FULL, "stage_ingest: %u tokens from position %u exceed KV capacity %u", n, m->pos_host, d.C);
+    if (m->first_stage) {
+        if (!tokens) return fail(NFAI_ERR_INVALID, "stage_ingest: tokens are required on the first stage");
+        if (hidden_in) return fail(NFAI_ERR_INVALID, "stage_ingest: the first stage embeds its tokens: hidden_in must be NULL");
+        for (uint32_t i = 0; i < n; i++)
+            if (tokens[i] >= d.V) return fail(NFAI_ERR_INVALID, "stage_ingest: token %u >= vocab %u", tokens[i], d.V);
+    } else {
+        if (!hidden_in) return fail(NFAI_ERR_INVALID, "stage_ingest: hidden_in is required on a non-first stage");
+        if (tokens) return fail(NFAI_ERR_INVALID, "stage_ingest: a non-first stage takes hidden_in: tokens must be NULL");
+    }
+    if (m->last_stage && hidden_out) return fail(NFAI_ERR_INVALID, "stage_ingest: the last stage forms no output rows: hidden_out must be NULL");
+    if (!m->last_stage && !hidden_out) return fail(NFAI_ERR_INVALID, "stage_ingest: hidden_out is required on a non-last stage");
+    if (m->first_stage && m->last_stage) return prefill_impl(h, tokens, n, nullptr, false);   // the whole network: nfai_hip_llama_ingest
+    if (m->h_pin[1]) return engine_failed(m, m->h_pin[1]);   // as nfai_hip_llama_stage_step
+    hipStream_t s = m->ctx->stream;
+    const float *in = static_cast<const float *>(hidden_in);
+    float *out = static_cast<float *>(hidden_out);
+    if (prefill_mfma_rules(m, m->first_stage)) {
+        S_TRY(ensure_wide_shadow(m));
+        for (uint32_t done = 0; done < n;) {
+            const uint32_t T = std::min(n - done, d.max_batch);
+            S_TRY(prefill_chunk(m, m->first_stage ? tokens + done : nullptr, T, in ? in + (size_t)done * d.E : nullptr,
+                                out ? out + (size_t)done * d.E : nullptr, true));
+            done += T;
+        }
+    } else {
+        // no MFMA workspace / rules not met: the body of nfai_hip_llama_stage_step n times, row i in -> row i out (bit-identical to n
+        // stage steps; the launches are enqueued directly instead of through the stage graph, which is captured per buffer pair)
+        for (uint32_t i = 0; i < n; i++) {
+            if (m->first_stage) S_TRY(set_token_async(m, tokens[i]));
+            S_TRY(stage_enqueue(m, in ? in + (size_t)i * d.E : nullptr, out ? out + (size_t)i * d.E : nullptr));
+            m->pos_host++;
+        }
+    }
+    // `tokens` is the caller's pageable memory: the first stage returns once every copy out of it has run
+    if (m->first_stage) HIP_TRY(hipStreamSynchronize(s));
     return NFAI_OK;
 }
 
@@ -1745,6 +1829,16 @@ NFAI_API int32_t nfai_hip_llama_profile_step(nfai_model_t h, uint32_t token, flo
         ms_by_class[m->ev_class[i]] += ms;
         launches_by_class[m->ev_class[i]]++;
     }
+    return NFAI_OK;
+}
+
+// Test hook (not in nfai_hip.h): where the model's fp16 copies of its K-quant matrices live and how many bytes they take (0 / NULL
+// before the first prefill); slots that share a donor's tensors report the donor's (tests/test_gpu_pipeline_ingest.py).
+NFAI_API int32_t nfai_hip_debug_prefill_shadow(nfai_model_t h, void **ptr, uint64_t *bytes)
+{
+    MODEL_OR_FAIL(m, h);
+    if (ptr) *ptr = m->pf.wide->ptr;
+    if (bytes) *bytes = m->pf.wide->bytes;
     return NFAI_OK;
 }
 

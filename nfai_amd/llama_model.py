@@ -230,6 +230,18 @@ class LlamaModel:
              logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None, C.byref(am) if (want_argmax or want_logits) else None)
         return logits, am.value
 
+    def StageIngest(self, tokens=None, hidden_in: int | None = None, hidden_out: int | None = None, n: int | None = None) -> None:
+        """The prompt phase of this pipeline stage (nfai_hip_llama_stage_ingest): n prompt tokens' K / V rows, nothing sampled.
+        First stage: `tokens` (host); other stages: `hidden_in` = device address of [n][E] fp32 rows; non-last stages: `hidden_out`
+        = device address of [n][E] fp32 rows for the next stage.  n defaults to len(tokens)."""
+        t = None if tokens is None else np.ascontiguousarray(tokens, np.uint32)
+        if n is None:
+            if t is None:
+                raise ValueError("StageIngest: n is required without tokens")
+            n = t.size
+        call("nfai_hip_llama_stage_ingest", self.handle, None if t is None else t.ctypes.data_as(C.POINTER(C.c_uint32)),
+             C.c_void_p(hidden_in), C.c_void_p(hidden_out), int(n))
+
     def TokenToDevice(self, dst_ptr: int) -> None:
         call("nfai_hip_llama_token_to_device", self.handle, C.c_void_p(dst_ptr))
 

@@ -144,6 +144,88 @@ def run_schedule_in_process(stages, n_steps: int, first_tokens, copy, n_slots: i
         assert n_s == n_r, "every receive of a tick has its send in the same tick"
 
 
+def prompt_jobs(prompt_lengths, chunk: int) -> list[tuple[int, int, int]]:
+    """The (slot, first position, rows) jobs of the prompt phase: chunk c of every slot before chunk c + 1 of any, slots in order
+    within a round; a slot's last chunk may be short, a slot with an empty prompt has no jobs."""
+    assert chunk >= 1
+    n_chunks = [(int(n) + chunk - 1) // chunk for n in prompt_lengths]
+    jobs = []
+    for c in range(max(n_chunks, default=0)):
+        for slot, n in enumerate(prompt_lengths):
+            if c < n_chunks[slot]:
+                jobs.append((slot, c * chunk, min(chunk, int(n) - c * chunk)))
+    return jobs
+
+
+def schedule_prompt_ticks(stage, rank: int, world: int, prompt_lengths, chunk: int, prompts=None):
+    """The prompt phase of every slot (all prompt tokens but the last: their K / V rows, nothing sampled) as a wavefront of chunks:
+    jobs are (slot, chunk) pairs in the order of `prompt_jobs`; stage r runs job j at tick j + r, then posts ONE exchange batch (its
+    [T][E] output rows to r + 1, the next job's rows from r - 1).  Both ends of every link post in the same tick, as in
+    `schedule_ticks`, so the schedule cannot deadlock under RCCL or gloo.  Every stage runs the jobs in the same order, so chunk c of
+    a slot reaches each stage after chunk c - 1 (KV positions in order).  No token travels back: the last stage samples nothing.
+    n_jobs + world - 1 ticks.
+
+    A sent or received buffer is a view of exactly T x E floats; T >= 1 and E > 1, so it never has the single element by which the
+    exchange (RcclComm.exchange) recognises a token word.
+
+    stage API: prompt_first(slot, begin, n, tokens) [rank 0; tokens = prompts[slot][begin:begin + n], or None without `prompts`],
+    prompt_middle(slot, n), prompt_last(slot, n); buffers p_in(slot, n), p_out(slot, n).  world == 1: prompt_first only.
+
+    The prompt -> decode recipe: `run_prompt_schedule(..., [p[:-1] for p in prompts], chunk)`, then
+    `run_schedule(..., first_tokens=[p[-1] for p in prompts])` — the last prompt token is the first sampled step."""
+    last = world - 1
+    jobs = prompt_jobs(prompt_lengths, chunk)
+    n_jobs = len(jobs)
+    for tick in range(n_jobs + world - 1):
+        j = tick - rank
+        sends, recvs = [], []
+        if 0 <= j < n_jobs:
+            slot, begin, n = jobs[j]
+            if rank == 0:
+                toks = None if prompts is None else prompts[slot][begin:begin + n]
+                stage.prompt_first(slot, begin, n, toks)
+            elif rank < last:
+                stage.prompt_middle(slot, n)
+            else:
+                stage.prompt_last(slot, n)
+            if rank < last:
+                sends.append((stage.p_out(slot, n), rank + 1))
+        j2 = tick + 1 - rank
+        if rank > 0 and 0 <= j2 < n_jobs:
+            slot2, _, n2 = jobs[j2]
+            recvs.append((stage.p_in(slot2, n2), rank - 1))
+        yield sends, recvs
+
+
+def run_prompt_schedule(stage, comm, rank: int, world: int, prompts_minus_last, chunk: int):
+    """One rank's side of the prompt phase (one process per GPU), as `run_schedule`: one exchange per tick with something posted,
+    comm.check() (when the comm has one) once per batch of `world` ticks.  prompts_minus_last[slot]: the slot's prompt without its
+    last token (only rank 0 reads the tokens; the other ranks only need the lengths)."""
+    check = getattr(comm, "check", None)
+    lengths = [len(p) for p in prompts_minus_last]
+    for tick, (sends, recvs) in enumerate(schedule_prompt_ticks(stage, rank, world, lengths, chunk, prompts_minus_last)):
+        if sends or recvs:
+            comm.exchange(sends, recvs)
+        if check is not None and tick % world == world - 1:
+            check()
+
+
+def run_prompt_schedule_in_process(stages, prompts_minus_last, chunk: int, copy):
+    """All stages of the prompt phase driven by ONE process in lock step, as `run_schedule_in_process`."""
+    world = len(stages)
+    lengths = [len(p) for p in prompts_minus_last]
+    gens = [schedule_prompt_ticks(st, r, world, lengths, chunk, prompts_minus_last) for r, st in enumerate(stages)]
+    for posted in zip(*gens):
+        for r, (sends, _) in enumerate(posted):
+            for buf, dst in sends:
+                match = [b for b, src in posted[dst][1] if src == r]
+                assert len(match) == 1, f"tick: rank {r} sends to {dst}, which posted {len(match)} receives from it"
+                copy(match[0], buf)
+        n_s = sum(len(s_) for s_, _ in posted)
+        n_r = sum(len(r_) for _, r_ in posted)
+        assert n_s == n_r, "every receive of a tick has its send in the same tick"
+
+
 class TorchComm:
     """torch.distributed point-to-point; one batch per tick (ncclGroupStart/End under RCCL)."""
 
@@ -260,7 +342,7 @@ class HipStage:
     """One pipeline stage on one GPU: `world` LlamaModel instances (one per in-flight sequence, each
     with its own KV cache and position) sharing one set of weights resident in HBM."""
 
-    def __init__(self, torch, mgr, dims, layer_range, weights, n_slots, capacity, rank, world, kv_f16=False, graph=True):
+    def __init__(self, torch, mgr, dims, layer_range, weights, n_slots, capacity, rank, world, kv_f16=False, graph=True, max_batch=0):
         from . import _lib
         from .llama_model import LlamaModel
         self.torch, self.rank, self.world = torch, rank, world
@@ -269,14 +351,19 @@ class HipStage:
         d = dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D,
                  rope_base=500000.0)
         # slot 0 owns the tensors (K-quant matrices are repacked into the T16 layout once, there); the other slots alias them
+        # max_batch > 0: every slot gets the MFMA prefill workspace of the prompt phase (prompt_* below, nfai_hip_llama_stage_ingest)
         self.models = [LlamaModel(mgr, {"general.name": dims.name}, tens, capacity, layer_range=layer_range, dims=d,
-                                  kv_f16=kv_f16, graph=graph)]
+                                  kv_f16=kv_f16, graph=graph, max_batch=max_batch)]
         for _ in range(1, n_slots):
             self.models.append(LlamaModel(mgr, {"general.name": dims.name}, tens, capacity, layer_range=layer_range, dims=d,
-                                          kv_f16=kv_f16, graph=graph, share_from=self.models[0]))
+                                          kv_f16=kv_f16, graph=graph, max_batch=max_batch, share_from=self.models[0]))
         self._hin = [torch.zeros(E, device="cuda", dtype=torch.float32) for _ in range(n_slots)]
         self._hout = [torch.zeros(E, device="cuda", dtype=torch.float32) for _ in range(n_slots)]
         self._tok = [torch.zeros(1, device="cuda", dtype=torch.int32) for _ in range(n_slots)]
+        # the prompt phase's hand-off rows, [max_batch][E] fp32 per slot (grown on demand for longer chunks)
+        self._E = E
+        self._pin = [torch.zeros(max_batch * E, device="cuda", dtype=torch.float32) for _ in range(n_slots)]
+        self._pout = [torch.zeros(max_batch * E, device="cuda", dtype=torch.float32) for _ in range(n_slots)]
         self._lib = _lib
 
     def h_in(self, s):
@@ -287,6 +374,27 @@ class HipStage:
 
     def tok(self, s):
         return self._tok[s]
+
+    def _rows(self, bufs, s, n):
+        if bufs[s].numel() < n * self._E:
+            bufs[s] = self.torch.zeros(n * self._E, device="cuda", dtype=self.torch.float32)
+        return bufs[s][: n * self._E]
+
+    def p_in(self, s, n):
+        return self._rows(self._pin, s, n)
+
+    def p_out(self, s, n):
+        return self._rows(self._pout, s, n)
+
+    def prompt_first(self, slot, begin, n, tokens):
+        out = None if self.world == 1 else self.p_out(slot, n).data_ptr()
+        self.models[slot].StageIngest(tokens, None, out, n)
+
+    def prompt_middle(self, slot, n):
+        self.models[slot].StageIngest(None, self.p_in(slot, n).data_ptr(), self.p_out(slot, n).data_ptr(), n)
+
+    def prompt_last(self, slot, n):
+        self.models[slot].StageIngest(None, self.p_in(slot, n).data_ptr(), None, n)
 
     def first(self, slot, token):
         m = self.models[slot]
