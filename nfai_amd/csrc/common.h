@@ -118,7 +118,7 @@ struct GemvArgs {
     // other blocks' launches and advances the hand-off epoch; this launch's own RoPE forms cos/sin itself
     struct Begin {
         bool on = false;
-        const void *emb = nullptr;   // [emb_rows][K]: F16 / F32 row-major, or the T16 layout of a Q4_K / Q6_K table
+        const void *emb = nullptr;   // [emb_rows][K]: F16 / F32 row-major, or the T16 layout of a Q4_K / Q6_K / Q8_0 table
         int emb_type = NFAI_F16;
         uint64_t emb_rows = 0;
         const uint32_t *tok = nullptr;
@@ -140,10 +140,18 @@ enum GemvMode { GEMV_PLAIN = 0, GEMV_RESIDUAL = 1, GEMV_QKV_ROPE = 2, GEMV_GATEU
 
 // Internal weight-type codes of the T16 layouts (kernels_gemv_kqm.hip): same bytes as the ggml type, rows
 // grouped in tiles of 16.  Never seen across the C ABI: uploads with rows % 16 == 0 are repacked into them.
-constexpr int NFAI_Q4_K_T16 = 112, NFAI_Q6_K_T16 = 114;
+// Q8_0 exists only in the T16 layout (rows % 16 == 0 is a rule of its upload); is_kquant covers it (block-quantised, same paths).
+constexpr int NFAI_Q8_0_T16 = 108, NFAI_Q4_K_T16 = 112, NFAI_Q6_K_T16 = 114;
 constexpr int NFAI_KQ_MIXED = 115;  // GemvArgs::w_type of a q|k|v launch whose segments are Q4_K_T16 / Q6_K_T16 per seg6_mask
-inline bool is_kquant(int t) { return t == NFAI_Q4_K || t == NFAI_Q6_K || t == NFAI_Q4_K_T16 || t == NFAI_Q6_K_T16; }
-inline int ggml_type_of(int t) { return t == NFAI_Q4_K_T16 ? NFAI_Q4_K : (t == NFAI_Q6_K_T16 ? NFAI_Q6_K : t); }
+inline bool is_kquant(int t)
+{
+    return t == NFAI_Q4_K || t == NFAI_Q6_K || t == NFAI_Q4_K_T16 || t == NFAI_Q6_K_T16 || t == NFAI_Q8_0 || t == NFAI_Q8_0_T16;
+}
+inline bool is_t16(int t) { return t == NFAI_Q4_K_T16 || t == NFAI_Q6_K_T16 || t == NFAI_Q8_0_T16; }
+inline int ggml_type_of(int t)
+{
+    return t == NFAI_Q4_K_T16 ? NFAI_Q4_K : (t == NFAI_Q6_K_T16 ? NFAI_Q6_K : (t == NFAI_Q8_0_T16 ? NFAI_Q8_0 : t));
+}
 
 hipError_t launch_gemv(const GemvArgs &a, hipStream_t s);     // any weight type; K-quants go to launch_gemv_kq / _kqm
 bool gemv_begin_ok(const GemvArgs &a);                         // can this q|k|v launch carry the per-token prologue (GemvArgs::Begin)?
@@ -155,9 +163,10 @@ hipError_t launch_gemv_kq(const GemvArgs &a, hipStream_t s);  // Q4_K (native bl
 hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s); // Q4_K_T16: MFMA dot products
 hipError_t launch_repack_q4k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
 hipError_t launch_repack_q6k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
+hipError_t launch_repack_q80_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
 hipError_t launch_embed_kqt(const void *table, int type, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E, hipStream_t s);
 hipError_t launch_embed_rows_kqt(const void *table, int type, uint64_t n_rows, const uint32_t *toks, float *y, uint32_t T, uint32_t E, hipStream_t s);
-hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64_t cols, void *out_f16, hipStream_t s);  // T16 K-quant -> fp16 [rows][cols]
+hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64_t cols, void *out_f16, hipStream_t s);  // T16 K-quant / Q8_0 -> fp16 [rows][cols]
 // Q6_K super-blocks are 210 bytes (not 16-byte aligned): in HBM they live as four planes
 // ql | qh | scales | d (same bytes, naturally aligned accesses).  nblk = rows * cols / 256.
 hipError_t launch_repack_q6k(const void *native, void *planes, uint64_t nblk, hipStream_t s);
@@ -434,7 +443,7 @@ struct BeginParams {
 };
 
 // four consecutive elements k .. k+3 (k % 4 == 0) of row `row` of an embedding table with E columns, widened to fp32 exactly as
-// TokenEmbedShader (TokenEmbedShader.cs:131-159) / k_embed_q4t / k_embed_q6t give them
+// TokenEmbedShader (TokenEmbedShader.cs:131-159) / k_embed_q4t / k_embed_q6t / k_embed_q8t give them
 __device__ __forceinline__ f32x4 embed_load4(const uint8_t *table, int type, uint64_t n_rows, uint64_t row, uint32_t k, uint32_t E)
 {
     typedef __attribute__((address_space(1))) uint8_t g8;
@@ -447,7 +456,14 @@ __device__ __forceinline__ f32x4 embed_load4(const uint8_t *table, int type, uin
     const uint32_t NB = E / 256, blk = k >> 8, kk = k & 255;
     const uint64_t tile = row >> 4, r = row & 15, tb = tile * NB + blk, nblk = n_rows * NB;
     f32x4 out;
-    if (type == NFAI_Q4_K_T16) {  // k_embed_q4t
+    if (type == NFAI_Q8_0_T16) {  // k_embed_q8t
+        const uint32_t ln = ((kk >> 4) & 3) * 16 + (uint32_t)r;
+        const uint32_t q4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t + tb * 4096 + (kk >> 6) * 1024 + ln * 16 + (kk & 15));
+        const uint32_t b32 = kk >> 5;  // its d: half (b32 & 1) * 4 + (b32 >> 1) of the row's 16 bytes
+        const float d = (float)reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(t + nblk * 256 + tb * 256 + r * 16)[(b32 & 1) * 4 + (b32 >> 1)];
+#pragma unroll
+        for (int e = 0; e < 4; e++) out[e] = d * (float)(int8_t)((q4 >> (8 * e)) & 0xFFu);
+    } else if (type == NFAI_Q4_K_T16) {  // k_embed_q4t
         const uint32_t sb = kk >> 5, l = kk & 31;
         const g8 *hdr = t + nblk * 128 + tb * 256 + r * 16;
         const float d = (float)*reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(hdr);

@@ -1,6 +1,6 @@
-// kernels_gemv_kqm.hip — decode GEMV on ggml K-quant weights, second generation: the integer dot products
+// kernels_gemv_kqm.hip — decode GEMV on ggml K-quant and Q8_0 weights, second generation: the integer dot products
 // of the quantised weights with fixed-point activations run on the matrix cores (v_mfma_i32_16x16x64_i8 used as
-// 64 independent 16-wide dot products per instruction), the K-quant scales are applied in fp32.
+// 64 independent 16-wide dot products per instruction), the K-quant / Q8_0 scales are applied in fp32.
 // Same op as kernels_gemv_kq.hip (MatrixMultiplyShader.cs:255-289 on weights the reference cannot
 // load at all, Parser.cs:111-114); that file stays as the path for row counts that are not a
 // multiple of 16.
@@ -16,7 +16,8 @@
 // scaled by a power of two so that |x * 2^S| < 2^22, rounded to an integer and split into three
 // signed base-256 digits; sum q * x' = S0 + 256 S1 + 65536 S2 is exact in int32, the K-quant scales
 // (d * sc, dmin * m, the -32 offset of Q6_K via the group sums of x') are applied in fp32 exactly
-// as ggml defines the block.  The only approximation is x' = round(x * 2^S): 24 bits relative to
+// as ggml defines the block; Q8_0 (d * q, q a signed byte) needs neither sums nor offsets: one d per lane
+// and MFMA.  The only approximation is x' = round(x * 2^S): 24 bits relative to
 // the largest |x| of the super-block.  Against the fp32 oracle the differences are at the level of
 // fp32 summation-order noise (tests/test_gpu_kquant.py states the tolerance; max |dlogit| 1.5e-5 at 3B).
 //
@@ -25,6 +26,10 @@
 //                  i.e. lane group G owns sub-blocks 2G (low nibbles) and 2G+1 (high nibbles) of its row;
 //         plane 1  [tile][blk][r:16][16 B]          d, dmin, 12 scale bytes of row 16*tile+r.
 //   Q6_K: see k_repack_q6k_t16.
+//   Q8_0: plane 0  [tile][blk][h:4][lane:64][16 B]  lane = G*16 + r holds qs bytes 64h + 16G .. +16 of super-block blk of
+//                  row 16*tile+r: 16 weights of ONE 32-block (2h + (G >> 1)), so one d per lane and MFMA;
+//         plane 1  [tile][blk][r:16][16 B]          the eight fp16 d of that row and super-block, d of 32-block b at half
+//                                                   (b & 1) * 4 + (b >> 1): lanes of group G read the 8 bytes of their four d.
 // Every wave-wide load is one contiguous kilobyte (quants) or 256 bytes (headers).
 //
 // Work split: a workgroup owns whole 16-row tiles ("units": one tile, or the gate and the up tile of
@@ -176,9 +181,11 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
     static_assert(!BEGIN || (MODE == GEMV_QKV_ROPE && NORM), "a token begins with a normed q|k|v launch");
     // QT = NFAI_KQ_MIXED (QKV only): Q4_K and Q6_K segments in one launch (Q4_K_M files keep attn_v in Q6_K on half of
     // the blocks); the activations are staged in both fragment layouts and every step branches on its segment's type.
-    constexpr bool HAS4 = QT != NFAI_Q6_K_T16, HAS6 = QT != NFAI_Q4_K_T16, MIXED = HAS4 && HAS6;
+    // QT = NFAI_Q8_0_T16: its own A-fragment layout, never mixed with the K-quants (llama.hip gives a Q8_0 segment its own launch).
+    constexpr bool HAS8 = QT == NFAI_Q8_0_T16;
+    constexpr bool HAS4 = !HAS8 && QT != NFAI_Q6_K_T16, HAS6 = !HAS8 && QT != NFAI_Q4_K_T16, MIXED = HAS4 && HAS6;
     static_assert(!MIXED || MODE == GEMV_QKV_ROPE, "mixed encodings exist for the q|k|v launch only");
-    using Regs = typename std::conditional<QT == NFAI_Q4_K_T16, Q4T, Q6T>::type;
+    using Regs = typename std::conditional<QT == NFAI_Q4_K_T16, Q4T, typename std::conditional<HAS8, Q8T, Q6T>::type>::type;
     constexpr int R = MODE == GEMV_GATEUP ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x, lane = tid & 63, nw = blockDim.x >> 6;
@@ -226,6 +233,9 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
     if constexpr (BEGIN) begin_bookkeeping(p.begin, pre0.pos, cs_lds);
     // ---- weights of the first steps
     constexpr int NBUF = NS > 0 ? NS : 2;
+    // Steps issued before the prologue.  Q8_0 with eight super-blocks per wave and the RMSNorm gains (K > 16384): x, the gains and two
+    // 18-VGPR steps did not fit 128 VGPRs together (scratch); the second step is issued once x is staged.
+    constexpr int PRE = (HAS8 && BPW == 8 && NORM && NS == 0) ? 1 : NBUF;
     Regs buf[NBUF];
     uint32_t ist = 0;
     auto issue = [&](Regs &buf) {
@@ -239,6 +249,8 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
             buf = q4t_load(p, seg, tile, blk, lane);
         } else if constexpr (QT == NFAI_Q6_K_T16) {
             buf = q6t_load(p, seg, tile, blk, lane);
+        } else if constexpr (HAS8) {
+            buf = q8t_load(p, seg, tile, blk, lane);
         } else {
             if ((p.seg6 >> seg) & 1u) {
                 buf = q6t_load(p, seg, tile, blk, lane);
@@ -250,7 +262,7 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
         ++ist;
     };
 #pragma unroll
-    for (int j = 0; j < NBUF; j++) issue(buf[j]);
+    for (int j = 0; j < PRE; j++) issue(buf[j]);
     STAMP(1);  // activation loads and the first weight steps issued
 
     // ---- prologue: per-super-block power-of-two scale, three base-256 digits -> LDS, scale-group sums.
@@ -282,10 +294,11 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
                 v[2] = v[2] * gv[i][2];
                 v[3] = v[3] * gv[i][3];
             }
-            kqm_stage<HAS4, HAS6>(v, blk, lane, xa, xa6, sums, sums6, scl);
+            kqm_stage<HAS4, HAS6, HAS8>(v, blk, lane, xa, xa6, sums, sums6, scl);
         }
         // no barrier: every LDS word written above is read only by this wave (LDS operations of a wave execute in order)
     }
+    if constexpr (PRE < NBUF) issue(buf[PRE]);
     STAMP(2);  // x normalised, scaled and staged as digits in LDS
 
     const uint32_t g = lane >> 4, ra = lane & 15;
@@ -316,16 +329,20 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
             for (int sl = 0; sl < 4; sl++) af[sl] = *reinterpret_cast<const i32x4 *>(abase + sl * 256);
         }
         const float inv_scale = scl[blk];
-        if (is6) {
-            if constexpr (HAS6) {
-                const f32x4 sm = *reinterpret_cast<const f32x4 *>(sums6 + (blk * 4 + g) * 4);
-                a = q6t_dot(buf, af, sm, g);
-            }
+        if constexpr (HAS8) {
+            a = q8t_dot(buf, af);
         } else {
-            if constexpr (HAS4) {
-                const f32x4 sm = *reinterpret_cast<const f32x4 *>(sums + (blk * 4 + g) * 4);
-                if constexpr (QT == NFAI_Q4_K_T16) a = q4t_dot(buf, af, f32x2{sm[0], sm[1]}, g);
-                else a = q4t_dot(Q4T{buf.qla, buf.qlb, buf.sc}, af, f32x2{sm[0], sm[1]}, g);
+            if (is6) {
+                if constexpr (HAS6) {
+                    const f32x4 sm = *reinterpret_cast<const f32x4 *>(sums6 + (blk * 4 + g) * 4);
+                    a = q6t_dot(buf, af, sm, g);
+                }
+            } else {
+                if constexpr (HAS4) {
+                    const f32x4 sm = *reinterpret_cast<const f32x4 *>(sums + (blk * 4 + g) * 4);
+                    if constexpr (QT == NFAI_Q4_K_T16) a = q4t_dot(buf, af, f32x2{sm[0], sm[1]}, g);
+                    else a = q4t_dot(Q4T{buf.qla, buf.qlb, buf.sc}, af, f32x2{sm[0], sm[1]}, g);
+                }
             }
         }
         acc += live ? a * inv_scale : 0.f;
@@ -491,6 +508,50 @@ hipError_t launch_repack_q6k_t16(const void *native, void *tiled, uint64_t rows,
     return hipGetLastError();
 }
 
+// ---- Q8_0 repack: native 34-byte blocks (row-major) -> T16 planes (same bytes; layout in the header comment) ------------
+__global__ void k_repack_q80_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
+{
+    const uint64_t tb = blockIdx.x;
+    const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB), t = threadIdx.x;
+    const uint64_t nblk = (uint64_t)n_tiles * 16 * NB;
+    // native blocks are only 2-byte aligned: byte copies
+    for (uint32_t e = t; e < 4096; e += blockDim.x) {
+        const uint32_t h = e >> 10, ln = (e >> 4) & 63, b = e & 15, G = ln >> 4, r = ln & 15, kk = 64 * h + 16 * G + b;
+        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB * 8 + blk * 8 + (kk >> 5)) * 34;
+        dst[tb * 4096 + e] = s[2 + (kk & 31)];
+    }
+    for (uint32_t e = t; e < 256; e += blockDim.x) {
+        const uint32_t r = e >> 4, i = (e & 15) >> 1, b32 = 2 * (i & 3) + (i >> 2);  // half i of the row = d of 32-block b32
+        dst[nblk * 256 + tb * 256 + e] = src[((uint64_t)(tile * 16 + r) * NB * 8 + blk * 8 + b32) * 34 + (e & 1)];
+    }
+}
+
+hipError_t launch_repack_q80_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
+{
+    if (rows == 0) return hipSuccess;
+    if (rows % 16 || cols % 256) return hipErrorInvalidValue;
+    const uint64_t nb = cols / 256, grid = rows / 16 * nb;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    k_repack_q80_t16<<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(native), static_cast<uint8_t *>(tiled), (uint32_t)(rows / 16),
+                                                    (uint32_t)nb);
+    return hipGetLastError();
+}
+
+__global__ void k_embed_q8t(const uint8_t *table, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= E) return;
+    tok += blockIdx.y;
+    y += (uint64_t)blockIdx.y * E;
+    const uint32_t NB = E / 256, blk = k >> 8, kk = k & 255;
+    const uint64_t row = tok[0], tile = row >> 4, r = row & 15, tb = tile * NB + blk, nblk = n_rows * NB;
+    const uint32_t ln = ((kk >> 4) & 3) * 16 + (uint32_t)r;
+    const int8_t q = (int8_t)table[tb * 4096 + (kk >> 6) * 1024 + ln * 16 + (kk & 15)];
+    const uint32_t b32 = kk >> 5;
+    const float d = (float)reinterpret_cast<const _Float16 *>(table + nblk * 256 + tb * 256 + r * 16)[(b32 & 1) * 4 + (b32 >> 1)];
+    y[k] = d * (float)q;
+}
+
 __global__ void k_embed_q6t(const uint8_t *table, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -534,6 +595,7 @@ hipError_t launch_embed_rows_kqt(const void *table, int type, uint64_t n_rows, c
     const dim3 grid((E + 255) / 256, T);
     if (type == NFAI_Q4_K_T16) k_embed_q4t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
     else if (type == NFAI_Q6_K_T16) k_embed_q6t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
+    else if (type == NFAI_Q8_0_T16) k_embed_q8t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -586,6 +648,21 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
                 *reinterpret_cast<f16x8 *>(orow + sb * 32 + c * 8) = o;
             }
         }
+    } else if constexpr (QT == NFAI_Q8_0_T16) {
+        const u32x4 dv = load_nt16(W + nblk * 256 + tb * 256 + r * 16);
+#pragma unroll
+        for (int h = 0; h < 4; h++) {  // weights 64h + 16g .. +16 of row r: 32-block 2h + (g >> 1), its d at half (g >> 1) * 4 + h
+            const u32x4 q = load_nt16(W + tb * 4096 + h * 1024 + lane * 16);
+            const uint32_t dw = (g >> 1) ? dv[2 + (h >> 1)] : dv[h >> 1];
+            const float d = (h & 1) ? h2f_hi(dw) : h2f_lo(dw);
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                f16x8 o;
+#pragma unroll
+                for (int e = 0; e < 8; e++) o[e] = (_Float16)(d * (float)(int8_t)((q[2 * c + (e >> 2)] >> (8 * (e & 3))) & 0xFFu));
+                *reinterpret_cast<f16x8 *>(orow + 64 * h + 16 * g + 8 * c) = o;
+            }
+        }
     } else {
         const u32x4 qla = load_nt16(W + tb * 3072 + lane * 16), qlb = load_nt16(W + tb * 3072 + 1024 + lane * 16);
         const u32x4 qh = load_nt16(W + tb * 3072 + 2048 + lane * 16);
@@ -634,6 +711,8 @@ hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64
         k_dequant_t16<NFAI_Q4_K_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
     else if (type == NFAI_Q6_K_T16)
         k_dequant_t16<NFAI_Q6_K_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
+    else if (type == NFAI_Q8_0_T16)
+        k_dequant_t16<NFAI_Q8_0_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -689,7 +768,7 @@ static hipError_t q4t_bpw(const KqmParams &p, int bpw, uint32_t grid, uint32_t b
 
 hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s)
 {
-    if (a.w_type != NFAI_Q4_K_T16 && a.w_type != NFAI_Q6_K_T16 && a.w_type != NFAI_KQ_MIXED) return hipErrorInvalidValue;
+    if (a.w_type != NFAI_Q4_K_T16 && a.w_type != NFAI_Q6_K_T16 && a.w_type != NFAI_Q8_0_T16 && a.w_type != NFAI_KQ_MIXED) return hipErrorInvalidValue;
     if (a.w_type == NFAI_KQ_MIXED && a.mode != GEMV_QKV_ROPE) return hipErrorInvalidValue;
     if (a.K == 0 || a.K % 256 != 0 || a.K > 32768) return hipErrorInvalidValue;
     KqmParams p{};
@@ -767,7 +846,14 @@ hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s)
         NFAI_STAMP_SET(p, names[a.mode & 3], grid, nw * 64);
     }
     if (a.w_type == NFAI_KQ_MIXED) return q4t_bpw<NFAI_KQ_MIXED, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
-    if (a.w_type == NFAI_Q4_K_T16) {
+    if (a.w_type == NFAI_Q8_0_T16) {
+        switch (a.mode) {
+            case GEMV_PLAIN: return q4t_bpw<NFAI_Q8_0_T16, GEMV_PLAIN>(p, bpw, grid, nw * 64, lds, s);
+            case GEMV_RESIDUAL: return q4t_bpw<NFAI_Q8_0_T16, GEMV_RESIDUAL>(p, bpw, grid, nw * 64, lds, s);
+            case GEMV_QKV_ROPE: return q4t_bpw<NFAI_Q8_0_T16, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
+            case GEMV_GATEUP: return q4t_bpw<NFAI_Q8_0_T16, GEMV_GATEUP>(p, bpw, grid, nw * 64, lds, s);
+        }
+    } else if (a.w_type == NFAI_Q4_K_T16) {
         switch (a.mode) {
             case GEMV_PLAIN: return q4t_bpw<NFAI_Q4_K_T16, GEMV_PLAIN>(p, bpw, grid, nw * 64, lds, s);
             case GEMV_RESIDUAL: return q4t_bpw<NFAI_Q4_K_T16, GEMV_RESIDUAL>(p, bpw, grid, nw * 64, lds, s);

@@ -37,6 +37,7 @@ struct KqmParams {
 };
 
 struct Q4T { u32x4 q0, q1, hdr; };
+struct Q8T { u32x4 q[4]; u32x2 d; };
 
 __device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t mask, uint32_t bits) { return (a & mask) | bits; }
 
@@ -64,6 +65,40 @@ __device__ __forceinline__ Q4T q4t_load_raw(const uint8_t *base, uint64_t n_tile
 __device__ __forceinline__ Q4T q4t_load(const KqmParams &p, uint32_t seg, uint32_t tile, uint32_t blk, uint32_t lane)
 {
     return q4t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
+}
+
+// One step of a wave on a Q8_0 T16 tensor: the quants (4 x 1 KiB) and the d of the 16 rows (256 B) of super-block `blk`; a lane of
+// group G takes the 8-byte half G >> 1 of its row's d: the d of its four 32-blocks 2h + (G >> 1), h = 0..3 (18 VGPRs per step with
+// the quants; with the 16 bytes of the row the q|k|v launch at K > 16384 spilled).
+__device__ __forceinline__ Q8T q8t_load_raw(const uint8_t *base, uint64_t n_tiles, uint32_t NB, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    const uint64_t tb = (uint64_t)tile * NB + blk;
+    const uint64_t nblk = n_tiles * 16 * NB;
+    Q8T r;
+#pragma unroll
+    for (int h = 0; h < 4; h++) r.q[h] = load_nt16(base + tb * 4096 + h * 1024 + lane * 16);
+    r.d = __builtin_nontemporal_load((const GLOBAL_AS u32x2 *)(base + nblk * 256 + tb * 256 + (lane & 15) * 16 + (lane >> 5) * 8));
+    return r;
+}
+
+__device__ __forceinline__ Q8T q8t_load(const KqmParams &p, uint32_t seg, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    return q8t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
+}
+
+// 64 weights of one lane: qs bytes 64h + 16G .. +16 of its row for h = 0..3 (block32 2h + (G >> 1)), already signed bytes: one MFMA and
+// one d per h, no offset and no min, so no sums of x'.  af: this lane's four A fragments (slot h).
+__device__ __forceinline__ float q8t_dot(const Q8T &w, const i32x4 (&af)[4])
+{
+    float a = 0.f;
+#pragma unroll
+    for (int h = 0; h < 4; h++) {
+        const i32x4 dq = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[h], __builtin_bit_cast(i32x4, w.q[h]), i32x4{0, 0, 0, 0}, 0, 0, 0);
+        const float v = fmaf((float)dq[2], 65536.0f, fmaf((float)dq[1], 256.0f, (float)dq[0]));
+        const float d = (h & 1) ? h2f_hi(w.d[h >> 1]) : h2f_lo(w.d[h >> 1]);
+        a = fmaf(d, v, a);
+    }
+    return a;
 }
 
 // 64 weights of one lane (sub-blocks 2G: low nibbles, 2G+1: high nibbles) against the activations.
@@ -105,9 +140,9 @@ __device__ __forceinline__ float q4t_dot(const Q4T &w, const i32x4 (&af)[4], f32
 
 // Fixed-point staging of ONE 256-element super-block of the activation vector by one wave (lane holds elements 4*lane .. +3, after the
 // optional RMSNorm): power-of-two scale so that |x * 2^S| < 2^22, three signed base-256 digits per element written as MFMA A
-// fragments [blk][slot:4][G][digit][16 B] (Q4_K layout in xa, Q6_K layout in xa6), the sums of x' per scale group and 2^-S.
-// Nothing written here is read by another wave.
-template <bool HAS4, bool HAS6>
+// fragments [blk][slot:4][G][digit][16 B] (Q4_K layout in xa, Q6_K layout in xa6, Q8_0 layout in xa), the sums of x' per scale group
+// (K-quants only) and 2^-S.  Nothing written here is read by another wave.
+template <bool HAS4, bool HAS6, bool HAS8 = false>
 __device__ __forceinline__ void kqm_stage(const f32x4 v, const uint32_t blk, const uint32_t lane, uint8_t *xa, uint8_t *xa6, float *sums,
                                           float *sums6, float *scl)
 {
@@ -136,6 +171,7 @@ __device__ __forceinline__ void kqm_stage(const f32x4 v, const uint32_t blk, con
     // A fragments [blk][slot:4][G][digit][16 bytes]; a lane reads slot s at +256*s from its (G, digit) base.
     //   Q4_K: k = (2G+n)*32 + hf*16 + j, slot = 2n + hf, sums per sub-block of 32 -> [blk][G][n]
     //   Q6_K: k = n*128 + qd*32 + lh*16 + j, G = 2n + lh, slot = qd, sums per group of 16 -> [blk][G][qd]
+    //   Q8_0: k = 64*slot + 16G + j, no sums
     const uint32_t j = k & 15;
     // sums over aligned groups of 4 lanes (16 elements) and of 8 lanes (32 elements)
     sx += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sx), 0xB1, 0xF, 0xF, true));
@@ -157,6 +193,13 @@ __device__ __forceinline__ void kqm_stage(const f32x4 v, const uint32_t blk, con
         *reinterpret_cast<uint32_t *>(frag + 16) = d1;
         *reinterpret_cast<uint32_t *>(frag + 32) = d2;
         if ((lane & 3) == 0) sums6[(blk * 4 + g) * 4 + slot] = sx16;
+    }
+    if constexpr (HAS8) {
+        const uint32_t g = (k >> 4) & 3, slot = k >> 6;
+        uint8_t *frag = xa + (size_t)blk * 1024 + (slot * 4 + g) * 64 + j;
+        *reinterpret_cast<uint32_t *>(frag) = d0;
+        *reinterpret_cast<uint32_t *>(frag + 16) = d1;
+        *reinterpret_cast<uint32_t *>(frag + 32) = d2;
     }
 }
 

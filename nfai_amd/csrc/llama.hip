@@ -51,6 +51,10 @@ struct WideShadow {
     ~WideShadow() { if (ptr) hipFree(ptr); }
 };
 
+// Does the MFMA prefill widen a matrix of this type to fp16?  Every quantised one; under NFAI_PREFILL_FUSED=1 (the K-quants take
+// the dequant-in-LDS GEMM) only Q8_0, which has no such GEMM.
+static bool prefill_widens(int type, bool fused) { return type != NFAI_F16 && (!fused || type == NFAI_Q8_0_T16); }
+
 enum KClass { KC_QKV = 0, KC_ATTN = 1, KC_WO = 2, KC_GATEUP = 3, KC_DOWN = 4, KC_LMHEAD = 5, KC_OTHER = 6, KC_ENGINE = 7, KC_N = 8 };
 
 constexpr uint32_t RING_LEN = 8192;
@@ -184,7 +188,7 @@ int check_shape(const char *what, const Tensor &t, uint64_t rows, uint64_t cols,
                     (unsigned long long)t.cols, (unsigned long long)rows, (unsigned long long)cols);
     if (!matrix && t.type != NFAI_F32) return fail(NFAI_ERR_UNSUPPORTED, "finalize: norm gain %s must be F32 (type %d)", what, t.type);
     if (matrix && t.type != NFAI_F16 && t.type != NFAI_F32 && !is_kquant(t.type))
-        return fail(NFAI_ERR_UNSUPPORTED, "finalize: matrix %s has ggml type %d; kernels exist for F16/F32/Q4_K/Q6_K", what, t.type);
+        return fail(NFAI_ERR_UNSUPPORTED, "finalize: matrix %s has ggml type %d; kernels exist for F16/F32/Q4_K/Q6_K/Q8_0", what, t.type);
     return NFAI_OK;
 }
 
@@ -334,12 +338,13 @@ GemvArgs gemv_base(Model *m, const Tensor &w, const float *x, uint32_t K)
 
 // [RMSNorm + Wq, Wk, Wv + RoPE + KV write] of block L on the activation vector x (TransformerBlock.cs:129-141).
 // One launch when q, k, v share an encoding; Q4_K_M files keep attn_v in Q6_K on some blocks: then the segments that differ get
-// their own launch (same kernel family, same epilogue).  qkv_launch: the launch that starts at segment `first` (-> `last`).
+// their own launch (same kernel family, same epilogue).  A Q8_0 segment is never mixed with K-quant segments: it shares a launch only
+// with other Q8_0 segments.  qkv_launch: the launch that starts at segment `first` (-> `last`).
 GemvArgs qkv_launch(Model *m, Layer &L, const float *x, int first, int &last)
 {
     const nfai_llama_desc &d = m->d;
     const Tensor *seg[3] = {&L.wq, &L.wk, &L.wv};
-    auto t16 = [](int ty) { return ty == NFAI_Q4_K_T16 || ty == NFAI_Q6_K_T16; };
+    auto t16 = [](int ty) { return ty == NFAI_Q4_K_T16 || ty == NFAI_Q6_K_T16; };  // the K-quants of the mixed kernel
     last = first;
     // segments of one encoding share a launch; so do T16 Q4_K and Q6_K segments (mixed kernel, kernels_gemv_kqm.hip)
     while (last + 1 < 3 && (seg[last + 1]->type == seg[first]->type || (t16(seg[last + 1]->type) && t16(seg[first]->type)))) last++;
@@ -486,14 +491,14 @@ int enqueue_token(Model *m, bool with_head)
     // the streaming GEMV kernels and the table is in a layout they read; otherwise it is its own launch.
     GemvArgs::Begin begin;
     {
-        auto streams = [](int ty) { return ty == NFAI_F16 || ty == NFAI_F32 || ty == NFAI_Q4_K_T16 || ty == NFAI_Q6_K_T16; };
+        auto streams = [](int ty) { return ty == NFAI_F16 || ty == NFAI_F32 || is_t16(ty); };
         const int et = m->token_embd.type;
         static const bool env_off = getenv("NFAI_BEGIN_FUSED") && atoi(getenv("NFAI_BEGIN_FUSED")) == 0;
         const bool engine_path = engine_ok(m) && m->eng_plans.size() == m->layers.size();
         int last0;
         const GemvArgs first_qkv = qkv_launch(m, m->layers[0], m->x, 0, last0);
         begin.on = !env_off && !m->unfused && !engine_path && gemv_begin_ok(first_qkv) && nfreq * 2 <= 128 &&
-                   (!m->first_stage || streams(et)) && (!m->first_stage || (et != NFAI_Q4_K_T16 && et != NFAI_Q6_K_T16) || d.E % 256 == 0);
+                   (!m->first_stage || streams(et)) && (!m->first_stage || !is_t16(et) || d.E % 256 == 0);
         if (begin.on) {
             if (m->first_stage) {
                 begin.emb = m->token_embd.ptr; begin.emb_type = et; begin.emb_rows = m->token_embd.rows;
@@ -553,7 +558,7 @@ int enqueue_token(Model *m, bool with_head)
         a.y = m->logits;
         // SamplingUtils.ArgMax + the end-of-token bookkeeping ride on the lm_head launch (LlamaModel.cs:125-130 in one launch): the
         // streaming GEMV kernels take it; the fallback kernel for K-quant tensors whose rows are not a multiple of 16 does not
-        const bool am_fused = head.type == NFAI_F16 || head.type == NFAI_F32 || head.type == NFAI_Q4_K_T16 || head.type == NFAI_Q6_K_T16;
+        const bool am_fused = head.type == NFAI_F16 || head.type == NFAI_F32 || is_t16(head.type);
         if (am_fused) {
             a.argmax_part = static_cast<char *>(m->d_argmax_part) + 4096;
             a.argmax_out = m->d_tok; a.argmax_pos_inc = m->d_pos; a.argmax_ring = m->d_ring; a.argmax_ring_len = RING_LEN;
@@ -850,10 +855,14 @@ static int set_tensor_impl(Model *m, const char *name, int type, uint64_t rows, 
     Tensor nt;
     nt.type = type; nt.rows = rows; nt.cols = cols; nt.bytes = rb * rows;
     hipStream_t s = m->ctx->stream;
+    if (type == NFAI_Q8_0 && (rows == 0 || rows % 16))
+        return fail(NFAI_ERR_UNSUPPORTED, "set_tensor(%s): Q8_0 needs rows %% 16 == 0, cols %% 256 == 0 and cols <= 32768 (%llu x %llu)", name,
+                    (unsigned long long)rows, (unsigned long long)cols);
     const bool q4_t16 = type == NFAI_Q4_K && rows > 0 && rows % 16 == 0, q6_t16 = type == NFAI_Q6_K && rows > 0 && rows % 16 == 0;
+    const bool q8_t16 = type == NFAI_Q8_0;
     auto fail_free = [&](void *a, void *b, int rc) { if (a) hipFree(a); if (b) hipFree(b); return rc; };
-    if (type == NFAI_Q6_K || q4_t16) {
-        // native blocks (host or device) -> owned repacked copy: Q6_K planes (common.h), Q4_K / Q6_K T16 tiles (kernels_gemv_kqm.hip)
+    if (type == NFAI_Q6_K || q4_t16 || q8_t16) {
+        // native blocks (host or device) -> owned repacked copy: Q6_K planes (common.h), Q4_K / Q6_K / Q8_0 T16 tiles (kernels_gemv_kqm.hip)
         void *native = dev, *staged = nullptr;
         if (!dev) {
             int rc = dalloc(&staged, nt.bytes, s);
@@ -867,11 +876,13 @@ static int set_tensor_impl(Model *m, const char *name, int type, uint64_t rows, 
         nt.owned = true;
         hipError_t e = q4_t16 ? launch_repack_q4k_t16(native, nt.ptr, rows, cols, s)
                      : q6_t16 ? launch_repack_q6k_t16(native, nt.ptr, rows, cols, s)
+                     : q8_t16 ? launch_repack_q80_t16(native, nt.ptr, rows, cols, s)
                               : launch_repack_q6k(native, nt.ptr, rows * cols / 256, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return fail_free(staged, nt.ptr, fail(NFAI_ERR_HIP, "set_tensor(%s): K-quant repack failed: %s", name, hipGetErrorString(e)));
         if (q4_t16) nt.type = NFAI_Q4_K_T16;
         if (q6_t16) nt.type = NFAI_Q6_K_T16;
+        if (q8_t16) nt.type = NFAI_Q8_0_T16;
         if (staged) hipFree(staged);
     } else if (dev) {
         nt.ptr = dev;
@@ -1297,13 +1308,13 @@ static int prefill_chunk(Model *m, const uint32_t *tokens, uint32_t T, const flo
     for (Layer &Lq : m->layers) {
         Layer L = Lq;
         WideShadow &wd = *w.wide;
-        if (widen && wd.ptr) {
+        if (wd.ptr) {   // (NFAI_PREFILL_FUSED=1: allocated only for Q8_0 matrices, ensure_wide_shadow)
             const size_t li = (size_t)(&Lq - m->layers.data());
             const bool kept = wd.all && wd.done[li];  // widened by an earlier chunk / prefill and still current
             uint64_t off = wd.all ? li * wd.slot : 0;
             const uint64_t end = off + wd.slot;
             for (Tensor *tq : {&L.wq, &L.wk, &L.wv, &L.wo, &L.wgate, &L.wup, &L.wdown}) {
-                if (tq->type == NFAI_F16) continue;
+                if (!prefill_widens(tq->type, !widen)) continue;
                 const uint64_t bytes = tq->rows * tq->cols * 2;
                 if (off + bytes > end) return fail(NFAI_ERR_STATE, "prefill: fp16 weight scratch too small");
                 void *dst = static_cast<uint8_t *>(wd.ptr) + off;
@@ -1423,10 +1434,10 @@ static bool prefill_mfma_rules(const Model *m, bool embeds)
     const nfai_llama_desc &d = m->d;
     if (d.E % 64 || d.F % 64 || (d.H * d.D) % 64 || (d.Hkv * d.D) % 64) return false;
     const int et = m->token_embd.type;
-    if (embeds && et != NFAI_F16 && et != NFAI_F32 && et != NFAI_Q4_K_T16 && et != NFAI_Q6_K_T16) return false;
+    if (embeds && et != NFAI_F16 && et != NFAI_F32 && !is_t16(et)) return false;
     for (const Layer &L : m->layers)
         for (const Tensor *t : {&L.wq, &L.wk, &L.wv, &L.wo, &L.wgate, &L.wup, &L.wdown})
-            if (t->type != NFAI_F16 && t->type != NFAI_Q4_K_T16 && t->type != NFAI_Q6_K_T16) return false;
+            if (t->type != NFAI_F16 && !is_t16(t->type)) return false;
     return true;
 }
 
@@ -1436,12 +1447,13 @@ static bool prefill_mfma_ok(const Model *m) { return m->first_stage && m->last_s
 static int ensure_wide_shadow(Model *m)
 {
     WideShadow &wd = *m->pf.wide;
-    if (wd.ptr || (getenv("NFAI_PREFILL_FUSED") && atoi(getenv("NFAI_PREFILL_FUSED")))) return NFAI_OK;
+    if (wd.ptr) return NFAI_OK;
+    const bool fused = getenv("NFAI_PREFILL_FUSED") && atoi(getenv("NFAI_PREFILL_FUSED"));
     uint64_t need = 0;
     for (const Layer &L : m->layers) {
         uint64_t b = 0;
         for (const Tensor *t : {&L.wq, &L.wk, &L.wv, &L.wo, &L.wgate, &L.wup, &L.wdown})
-            if (t->type != NFAI_F16) b += (t->rows * t->cols * 2 + 255) / 256 * 256;
+            if (prefill_widens(t->type, fused)) b += (t->rows * t->cols * 2 + 255) / 256 * 256;
         need = std::max(need, b);
     }
     if (!need) return NFAI_OK;
@@ -1496,7 +1508,7 @@ static int prefill_impl(nfai_model_t h, const uint32_t *tokens, uint32_t n, floa
         GemvArgs a = gemv_base(m, head, m->x, m->d.E);
         a.gamma = static_cast<const float *>(m->output_norm.ptr);
         a.y = m->logits;
-        const bool am_fused = head.type == NFAI_F16 || head.type == NFAI_F32 || head.type == NFAI_Q4_K_T16 || head.type == NFAI_Q6_K_T16;
+        const bool am_fused = head.type == NFAI_F16 || head.type == NFAI_F32 || is_t16(head.type);
         if (am_fused) {  // ArgMax in the lm_head launch, as in a decode step; no bookkeeping: the position was set above
             a.argmax_part = static_cast<char *>(m->d_argmax_part) + 4096;
             a.argmax_out = m->d_tok;

@@ -473,15 +473,17 @@ class PhaseWatchdog:
 
 def pipeline_costs(dims, quant: str) -> tuple[float, float]:
     """(bytes one block streams per token, bytes of the lm_head) under the file type: what partition_layers balances.  Q4_K_M files
-    keep attn_v / ffn_down in Q6_K on about half of the blocks (bench.tensor_type); the average block is used."""
+    keep attn_v / ffn_down in Q6_K on about half of the blocks (bench.tensor_type); the average block is used.  "q8_0": every
+    matrix in Q8_0, 8.5 bits per weight (34 bytes per 32)."""
     import bench as B
-    bits = {1: 16.0, B.Q4_K: 4.5, B.Q6_K: 6.5625}
+    bits = {1: 16.0, B.Q4_K: 4.5, B.Q6_K: 6.5625, 8: 8.5}
+    type_of = (lambda name: 8) if quant == "q8_0" else (lambda name: B.tensor_type(name, dims, quant))
     tot = 0.0
     for name, shape in dims.shapes().items():
         if name.startswith("blk.") and len(shape) == 2:
-            tot += shape[0] * shape[1] * bits[B.tensor_type(name, dims, quant)] / 8
+            tot += shape[0] * shape[1] * bits[type_of(name)] / 8
     head = "output.weight" if not dims.tied else "token_embd.weight"
-    return tot / dims.L, dims.V * dims.E * bits[B.tensor_type(head, dims, quant)] / 8
+    return tot / dims.L, dims.V * dims.E * bits[type_of(head)] / 8
 
 
 def run_bench_pipeline(args):

@@ -75,6 +75,22 @@ def make_weights(dims: LlamaDims, seed: int = 1234, std: float = 0.02) -> dict:
     return out
 
 
+def quantize_q8_0(W) -> bytes:
+    """ggml quantize_row_q8_0_ref on every row of W [rows][cols] (cols % 32 == 0): per 32-block d = amax / 127, q = round(x / d)
+    (roundf: halves away from zero), d stored as fp16; blocks of 34 bytes (fp16 d, int8 qs[32]), row-major."""
+    x = np.asarray(W, dtype=np.float32).reshape(-1, 32)
+    amax = np.abs(x).max(axis=1)
+    d = amax / np.float32(127)
+    inv = np.where(d != 0, np.float32(1) / np.where(d != 0, d, np.float32(1)), np.float32(0)).astype(np.float32)
+    v = x * inv[:, None]
+    t = np.trunc(v)
+    q = (t + np.sign(v) * (np.abs(v - t) >= np.float32(0.5))).astype(np.int8)  # roundf; v - t is exact
+    out = np.empty((x.shape[0], 34), np.uint8)
+    out[:, :2] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
+    out[:, 2:] = q.view(np.uint8)
+    return out.tobytes()
+
+
 def make_tokens(dims: LlamaDims, n: int, seed: int = 99) -> np.ndarray:
     rng = np.random.Generator(np.random.PCG64(seed))
     return rng.integers(0, dims.V, size=n, dtype=np.uint32)
