@@ -156,7 +156,7 @@ int32_t nfai_hip_topk(nfai_ctx_t ctx, nfai_buf_t x, uint32_t n, float temperatur
 
 /* ---- fused operators (no reference counterpart: each replaces the chain named) ---- */
 /* scores -> softmax -> weighted sum in one KV-cache pass, GQA heads sharing each K/V read.
- * K/V caches [C][Hkv*D] (reference layout), kv_type NFAI_F32 or NFAI_F16. */
+ * K/V caches [C][Hkv*D] (reference layout), kv_type NFAI_F32 or NFAI_F16; D 64 or 128, H/Hkv in {1, 2, 3, 4, 8}, C <= 32768. */
 int32_t nfai_hip_attn_decode(nfai_ctx_t ctx, nfai_buf_t q, nfai_buf_t kcache, nfai_buf_t vcache, nfai_buf_t o,
                              uint32_t H, uint32_t Hkv, uint32_t D, uint32_t S, uint32_t C, int32_t kv_type);
 /* [RMSNorm ->] GEMV [-> + residual]: y = res + W * (norm ? rmsnorm(x, gamma) : x).  gamma / res
@@ -244,6 +244,8 @@ typedef struct nfai_llama_desc {
     uint32_t max_batch;      /* prefill chunk capacity in tokens (0 = decode only) */
 } nfai_llama_desc;
 
+/* H/Hkv must be 1, 2, 3, 4 or 8 (NFAI_ERR_UNSUPPORTED otherwise) unless NFAI_LLAMA_UNFUSED, which takes any H/Hkv <= 8;
+ * D 64 or 128; C <= 32768. */
 int32_t nfai_hip_llama_create(nfai_ctx_t ctx, const nfai_llama_desc *desc, nfai_model_t *out);
 int32_t nfai_hip_llama_destroy(nfai_model_t model);
 /* GGUF tensor by name ("token_embd.weight", "blk.3.attn_q.weight", ..., "output_norm.weight",

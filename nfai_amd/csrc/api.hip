@@ -782,7 +782,7 @@ NFAI_API int32_t nfai_hip_attn_decode(nfai_ctx_t h, nfai_buf_t q, nfai_buf_t kc,
     a.pos_dev = scratch_pos(c);
     a.partials = scratch_attn(c);
     hipError_t e = launch_attn_decode(a, c->stream);
-    if (e == hipErrorInvalidValue) return fail(NFAI_ERR_INVALID, "attn_decode: unsupported shape (D must be 64 or 128, H/Hkv <= 8, C <= 32768)");
+    if (e == hipErrorInvalidValue) return fail(NFAI_ERR_INVALID, "attn_decode: unsupported shape (D must be 64 or 128, H/Hkv in {1, 2, 3, 4, 8}, C <= 32768)");
     if (e != hipSuccess) return fail(NFAI_ERR_HIP, "attn_decode: launch failed: %s", hipGetErrorString(e));
     return NFAI_OK;
 }

@@ -249,6 +249,8 @@ struct AttnArgs {
     uint32_t debug_withhold = 0;  // test hook: slice (value - 1) of kv head 0 publishes nothing, so the others' bounded waits give up
 };
 constexpr uint32_t ATTN_NSPLIT_MAX = 32;
+// query heads per kv head that the decode attention is instantiated for (k_attn_decode<…, G, …>)
+constexpr bool attn_group_ok(uint32_t G) { return G == 1 || G == 2 || G == 3 || G == 4 || G == 8; }
 size_t attn_partials_bytes(uint32_t H, uint32_t Hkv, uint32_t D, bool granules = false);  // granules: the {value, tag} form (AttnArgs::epoch set)
 hipError_t launch_attn_decode(const AttnArgs &a, hipStream_t s);
 size_t attn_wo_extra_bytes(uint32_t H, uint32_t D);  // workspace behind attn_partials_bytes(…, true) for the fused launch below

@@ -24,11 +24,15 @@
 //    meanwhile and apply it to the merged output: attention + Wo + residual in one launch.
 // The number of ACTIVE slices depends on the sequence length, which is read from device memory so
 // a captured hipGraph can be replayed for every position; inactive blocks exit at once.
+// Shapes: D = 64 or 128, G = H/Hkv in {1, 2, 3, 4, 8} (attn_group_ok; llama_create refuses other groupings for the fused path),
+// C <= 32768.  The LDS of a launch grows with G x C / 32; only G = 8 above ~31000 positions exceeds 64 KB (at most 67072 bytes),
+// and allow_lds raises the kernel's dynamic-LDS limit for it (gfx950: 160 KB per CU).
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
+#include <atomic>
 #include <mutex>
 
 namespace nfai {
@@ -36,7 +40,6 @@ namespace nfai {
 constexpr int ATTN_BLOCK = 256;
 constexpr int ATTN_MIN_CHUNK = 32;    // positions per slice before another slice is opened (swept 16..96 at 3B, context 520-776: 32 is best by 1.5 %)
 constexpr int ATTN_MAX_CHUNK = 1024;  // LDS score capacity per query head (positions)
-constexpr int ATTN_GMAX = 8;          // max query heads per kv head
 
 struct AttnParams {
     const float *q;
@@ -728,32 +731,59 @@ static bool grid_resident(K kernel, uint32_t threads, size_t lds, uint32_t block
     return memo_per_cu > 0 && (uint64_t)memo_per_cu * n_cu >= blocks;
 }
 
+// Dynamic LDS above 64 KB must be allowed per kernel (gfx950: 160 KB per CU).  Only G = 8 at capacities above 31232 (D = 64) /
+// 31744 (D = 128) positions needs it; the attribute is set once per instantiation, before the occupancy query and the launch.
+template <int LPP, int G, bool F16, bool ONLINE, bool POLL>
+static hipError_t allow_lds(size_t lds)
+{
+    static std::atomic<bool> done{false};
+    if (lds <= 64 * 1024 || done.load(std::memory_order_acquire)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_attn_decode<LPP, G, F16, ONLINE, POLL>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) done.store(true, std::memory_order_release);
+    return e;
+}
+
+template <int LPP, int G, bool F16, bool ONLINE, bool POLL>
+static bool resident_g(dim3 grid, size_t lds, uint32_t n_cu)
+{
+    if (allow_lds<LPP, G, F16, ONLINE, POLL>(lds) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return grid_resident(k_attn_decode<LPP, G, F16, ONLINE, POLL>, ATTN_BLOCK, lds, grid.x * grid.y, n_cu);
+}
+
 template <int LPP, bool F16, bool ONLINE, bool POLL>
 static bool resident_gp(uint32_t G, dim3 grid, size_t lds, uint32_t n_cu)
 {
-    const uint32_t blocks = grid.x * grid.y;
     switch (G) {
-        case 1: return grid_resident(k_attn_decode<LPP, 1, F16, ONLINE, POLL>, ATTN_BLOCK, lds, blocks, n_cu);
-        case 2: return grid_resident(k_attn_decode<LPP, 2, F16, ONLINE, POLL>, ATTN_BLOCK, lds, blocks, n_cu);
-        case 3: return grid_resident(k_attn_decode<LPP, 3, F16, ONLINE, POLL>, ATTN_BLOCK, lds, blocks, n_cu);
-        case 4: return grid_resident(k_attn_decode<LPP, 4, F16, ONLINE, POLL>, ATTN_BLOCK, lds, blocks, n_cu);
-        case 8: return grid_resident(k_attn_decode<LPP, 8, F16, ONLINE, POLL>, ATTN_BLOCK, lds, blocks, n_cu);
+        case 1: return resident_g<LPP, 1, F16, ONLINE, POLL>(grid, lds, n_cu);
+        case 2: return resident_g<LPP, 2, F16, ONLINE, POLL>(grid, lds, n_cu);
+        case 3: return resident_g<LPP, 3, F16, ONLINE, POLL>(grid, lds, n_cu);
+        case 4: return resident_g<LPP, 4, F16, ONLINE, POLL>(grid, lds, n_cu);
+        case 8: return resident_g<LPP, 8, F16, ONLINE, POLL>(grid, lds, n_cu);
     }
     return false;
+}
+
+template <int LPP, int G, bool F16, bool ONLINE, bool POLL>
+static hipError_t launch_one(const AttnParams &p, dim3 grid, size_t lds, hipStream_t s)
+{
+    const hipError_t e = allow_lds<LPP, G, F16, ONLINE, POLL>(lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_attn_decode<LPP, G, F16, ONLINE, POLL>), grid, dim3(ATTN_BLOCK), lds, s, p);
+    return hipGetLastError();
 }
 
 template <int LPP, bool F16, bool ONLINE, bool POLL>
 static hipError_t launch_gp(const AttnParams &p, uint32_t G, dim3 grid, size_t lds, hipStream_t s)
 {
     switch (G) {
-        case 1: hipLaunchKernelGGL((k_attn_decode<LPP, 1, F16, ONLINE, POLL>), grid, dim3(ATTN_BLOCK), lds, s, p); break;
-        case 2: hipLaunchKernelGGL((k_attn_decode<LPP, 2, F16, ONLINE, POLL>), grid, dim3(ATTN_BLOCK), lds, s, p); break;
-        case 3: hipLaunchKernelGGL((k_attn_decode<LPP, 3, F16, ONLINE, POLL>), grid, dim3(ATTN_BLOCK), lds, s, p); break;
-        case 4: hipLaunchKernelGGL((k_attn_decode<LPP, 4, F16, ONLINE, POLL>), grid, dim3(ATTN_BLOCK), lds, s, p); break;
-        case 8: hipLaunchKernelGGL((k_attn_decode<LPP, 8, F16, ONLINE, POLL>), grid, dim3(ATTN_BLOCK), lds, s, p); break;
-        default: return hipErrorInvalidValue;
+        case 1: return launch_one<LPP, 1, F16, ONLINE, POLL>(p, grid, lds, s);
+        case 2: return launch_one<LPP, 2, F16, ONLINE, POLL>(p, grid, lds, s);
+        case 3: return launch_one<LPP, 3, F16, ONLINE, POLL>(p, grid, lds, s);
+        case 4: return launch_one<LPP, 4, F16, ONLINE, POLL>(p, grid, lds, s);
+        case 8: return launch_one<LPP, 8, F16, ONLINE, POLL>(p, grid, lds, s);
     }
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 template <int LPP, bool F16, bool ONLINE>
@@ -769,7 +799,7 @@ static hipError_t fill_params(const AttnArgs &a, AttnParams &p, dim3 &grid, size
 {
     if (a.Hkv == 0 || a.H % a.Hkv != 0 || a.Hkv > 64) return hipErrorInvalidValue;
     const uint32_t G = a.H / a.Hkv;
-    if (G > ATTN_GMAX) return hipErrorInvalidValue;
+    if (!attn_group_ok(G)) return hipErrorInvalidValue;
     if (a.D != 64 && a.D != 128) return hipErrorInvalidValue;
     p.q = a.q; p.kc = a.kcache; p.vc = a.vcache;
     p.pos_stride = a.kv_pos_stride; p.head_stride = a.kv_head_stride;
@@ -797,7 +827,7 @@ static hipError_t fill_params(const AttnArgs &a, AttnParams &p, dim3 &grid, size
     if (max_chunk < 2 * ATTN_NSPLIT_MAX) max_chunk = 2 * ATTN_NSPLIT_MAX;
     const uint32_t lpp = a.D / 4, ngrp = ATTN_BLOCK / lpp;
     lds = (64 + (size_t)G * max_chunk + (size_t)G * ngrp * a.D + 64 + (size_t)G * ngrp * 2) * sizeof(float);  // + group stats of the one-pass form
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    if (lds > 160 * 1024) return hipErrorInvalidValue;  // (at most 67072 bytes: G = 8, D = 64, C = 32768; above 64 KB see allow_lds)
     grid = dim3(a.Hkv, p.max_split);
     // One-pass (online softmax, v_exp_f32) or two-pass form.  The position is device-side, so the choice is made from the KV
     // capacity the model was created with: above 2048 positions the one-pass form (8192 positions: 520 vs 493 tokens/s at

@@ -688,6 +688,10 @@ NFAI_API int32_t nfai_hip_llama_create(nfai_ctx_t ch, const nfai_llama_desc *des
     const nfai_llama_desc &d = *desc;
     NFAI_REQUIRE(d.E && d.L && d.H && d.Hkv && d.D && d.F && d.V && d.C, "llama_create: zero dimension");
     NFAI_REQUIRE(d.H % d.Hkv == 0 && d.H / d.Hkv <= 8, "llama_create: H=%u must be a multiple (<= 8x) of Hkv=%u", d.H, d.Hkv);
+    // the fused decode attention exists for G = H/Hkv in {1, 2, 3, 4, 8}; the 1:1 chain takes any G
+    if (!(d.flags & NFAI_LLAMA_UNFUSED) && !attn_group_ok(d.H / d.Hkv))
+        return fail(NFAI_ERR_UNSUPPORTED, "llama_create: H/Hkv = %u query heads per kv head (the fused decode takes 1, 2, 3, 4 or 8; "
+                                          "NFAI_LLAMA_UNFUSED takes any)", d.H / d.Hkv);
     NFAI_REQUIRE(d.D == 64 || d.D == 128, "llama_create: head_dim %u (kernels exist for 64 and 128)", d.D);
     NFAI_REQUIRE(d.E % 8 == 0 && d.F % 8 == 0 && (d.H * d.D) % 8 == 0, "llama_create: E, F, H*D must be multiples of 8");
     NFAI_REQUIRE(d.layer_begin < d.layer_end && d.layer_end <= d.L, "llama_create: layer range [%u,%u) outside [0,%u)", d.layer_begin,
@@ -1862,5 +1866,35 @@ NFAI_API int32_t nfai_hip_debug_attn_withhold(nfai_model_t h, uint32_t slice_plu
     HIP_TRY(hipStreamSynchronize(m->ctx->stream));
     m->dbg_withhold = slice_plus_1;
     drop_graphs(m);
+    return NFAI_OK;
+}
+
+// Test hook (not in nfai_hip.h): K or V rows [pos, pos + n) of one block as fp32 [n][Hkv*D] (fp16 caches widened) with one
+// synchronisation, where nfai_hip_llama_read_kv takes one per row (tests/test_gpu_attention_depth.py reads up to 32768 rows).
+NFAI_API int32_t nfai_hip_debug_read_kv_rows(nfai_model_t h, uint32_t layer, int32_t is_v, uint32_t pos, uint32_t n, float *host)
+{
+    MODEL_OR_FAIL(m, h);
+    const nfai_llama_desc &d = m->d;
+    if (layer < d.layer_begin || layer >= d.layer_end || n == 0 || (uint64_t)pos + n > d.C || !host)
+        return fail(NFAI_ERR_INVALID, "read_kv_rows: layer %u rows [%u, %u + %u)", layer, pos, pos, n);
+    Layer &L = m->layers[layer - d.layer_begin];
+    const char *base = static_cast<const char *>(is_v ? L.vcache : L.kcache);
+    hipStream_t s = m->ctx->stream;
+    const size_t row = (size_t)d.Hkv * d.D, esz = m->kv_esz;
+    std::vector<uint16_t> tmp16;
+    if (m->kv_f16) tmp16.resize(row * n);
+    char *dst = m->kv_f16 ? reinterpret_cast<char *>(tmp16.data()) : reinterpret_cast<char *>(host);
+    for (uint32_t kh = 0; kh < d.Hkv; kh++) {  // one strided copy per kv head: D elements of each of the n positions
+        const uint64_t idx = (uint64_t)pos * m->kv_pos_stride + (uint64_t)kh * m->kv_head_stride;
+        HIP_TRY(hipMemcpy2DAsync(dst + (size_t)kh * d.D * esz, row * esz, base + idx * esz, m->kv_pos_stride * esz, (size_t)d.D * esz, n,
+                                 hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (m->kv_f16)
+        for (size_t i = 0; i < tmp16.size(); i++) {
+            _Float16 hv;
+            memcpy(&hv, &tmp16[i], 2);
+            host[i] = (float)hv;
+        }
     return NFAI_OK;
 }
