@@ -118,7 +118,7 @@ struct GemvArgs {
     // other blocks' launches and advances the hand-off epoch; this launch's own RoPE forms cos/sin itself
     struct Begin {
         bool on = false;
-        const void *emb = nullptr;   // [emb_rows][K]: F16 / F32 row-major, or the T16 layout of a Q4_K / Q6_K / Q8_0 table
+        const void *emb = nullptr;   // [emb_rows][K]: F16 / F32 row-major, or the T16 layout of a Q4_K / Q5_K / Q6_K / Q8_0 table
         int emb_type = NFAI_F16;
         uint64_t emb_rows = 0;
         const uint32_t *tok = nullptr;
@@ -140,17 +140,21 @@ enum GemvMode { GEMV_PLAIN = 0, GEMV_RESIDUAL = 1, GEMV_QKV_ROPE = 2, GEMV_GATEU
 
 // Internal weight-type codes of the T16 layouts (kernels_gemv_kqm.hip): same bytes as the ggml type, rows
 // grouped in tiles of 16.  Never seen across the C ABI: uploads with rows % 16 == 0 are repacked into them.
-// Q8_0 exists only in the T16 layout (rows % 16 == 0 is a rule of its upload); is_kquant covers it (block-quantised, same paths).
-constexpr int NFAI_Q8_0_T16 = 108, NFAI_Q4_K_T16 = 112, NFAI_Q6_K_T16 = 114;
-constexpr int NFAI_KQ_MIXED = 115;  // GemvArgs::w_type of a q|k|v launch whose segments are Q4_K_T16 / Q6_K_T16 per seg6_mask
+// Q8_0 and Q5_K exist only in the T16 layout (rows % 16 == 0 is a rule of their upload); is_kquant covers them (block-quantised,
+// same paths).
+constexpr int NFAI_Q8_0_T16 = 108, NFAI_Q4_K_T16 = 112, NFAI_Q5_K_T16 = 113, NFAI_Q6_K_T16 = 114;
+constexpr int NFAI_KQ_MIXED = 115;   // GemvArgs::w_type of a q|k|v launch whose segments are Q4_K_T16 / Q6_K_T16 per seg6_mask
+constexpr int NFAI_KQ_MIXED5 = 116;  // the same with Q5_K_T16 / Q6_K_T16 segments (Q5_K_M files)
 inline bool is_kquant(int t)
 {
-    return t == NFAI_Q4_K || t == NFAI_Q6_K || t == NFAI_Q4_K_T16 || t == NFAI_Q6_K_T16 || t == NFAI_Q8_0 || t == NFAI_Q8_0_T16;
+    return t == NFAI_Q4_K || t == NFAI_Q6_K || t == NFAI_Q4_K_T16 || t == NFAI_Q6_K_T16 || t == NFAI_Q8_0 || t == NFAI_Q8_0_T16 ||
+           t == NFAI_Q5_K || t == NFAI_Q5_K_T16;
 }
-inline bool is_t16(int t) { return t == NFAI_Q4_K_T16 || t == NFAI_Q6_K_T16 || t == NFAI_Q8_0_T16; }
+inline bool is_t16(int t) { return t == NFAI_Q4_K_T16 || t == NFAI_Q6_K_T16 || t == NFAI_Q8_0_T16 || t == NFAI_Q5_K_T16; }
 inline int ggml_type_of(int t)
 {
-    return t == NFAI_Q4_K_T16 ? NFAI_Q4_K : (t == NFAI_Q6_K_T16 ? NFAI_Q6_K : (t == NFAI_Q8_0_T16 ? NFAI_Q8_0 : t));
+    return t == NFAI_Q4_K_T16 ? NFAI_Q4_K
+                              : (t == NFAI_Q6_K_T16 ? NFAI_Q6_K : (t == NFAI_Q8_0_T16 ? NFAI_Q8_0 : (t == NFAI_Q5_K_T16 ? NFAI_Q5_K : t)));
 }
 
 hipError_t launch_gemv(const GemvArgs &a, hipStream_t s);     // any weight type; K-quants go to launch_gemv_kq / _kqm
@@ -164,6 +168,7 @@ hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s); // Q4_K_T16: MFMA 
 hipError_t launch_repack_q4k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
 hipError_t launch_repack_q6k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
 hipError_t launch_repack_q80_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
+hipError_t launch_repack_q5k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
 hipError_t launch_embed_kqt(const void *table, int type, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E, hipStream_t s);
 hipError_t launch_embed_rows_kqt(const void *table, int type, uint64_t n_rows, const uint32_t *toks, float *y, uint32_t T, uint32_t E, hipStream_t s);
 hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64_t cols, void *out_f16, hipStream_t s);  // T16 K-quant / Q8_0 -> fp16 [rows][cols]
@@ -445,7 +450,7 @@ struct BeginParams {
 };
 
 // four consecutive elements k .. k+3 (k % 4 == 0) of row `row` of an embedding table with E columns, widened to fp32 exactly as
-// TokenEmbedShader (TokenEmbedShader.cs:131-159) / k_embed_q4t / k_embed_q6t / k_embed_q8t give them
+// TokenEmbedShader (TokenEmbedShader.cs:131-159) / k_embed_q4t / k_embed_q5t / k_embed_q6t / k_embed_q8t give them
 __device__ __forceinline__ f32x4 embed_load4(const uint8_t *table, int type, uint64_t n_rows, uint64_t row, uint32_t k, uint32_t E)
 {
     typedef __attribute__((address_space(1))) uint8_t g8;
@@ -465,7 +470,7 @@ __device__ __forceinline__ f32x4 embed_load4(const uint8_t *table, int type, uin
         const float d = (float)reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(t + nblk * 256 + tb * 256 + r * 16)[(b32 & 1) * 4 + (b32 >> 1)];
 #pragma unroll
         for (int e = 0; e < 4; e++) out[e] = d * (float)(int8_t)((q4 >> (8 * e)) & 0xFFu);
-    } else if (type == NFAI_Q4_K_T16) {  // k_embed_q4t
+    } else if (type == NFAI_Q4_K_T16 || type == NFAI_Q5_K_T16) {  // k_embed_q4t / k_embed_q5t
         const uint32_t sb = kk >> 5, l = kk & 31;
         const g8 *hdr = t + nblk * 128 + tb * 256 + r * 16;
         const float d = (float)*reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(hdr);
@@ -475,10 +480,15 @@ __device__ __forceinline__ f32x4 embed_load4(const uint8_t *table, int type, uin
         if (sb < 4) { sc = scales[sb] & 63; m = scales[sb + 4] & 63; }
         else { sc = (scales[sb + 4] & 0xF) | ((scales[sb - 4] >> 6) << 4); m = (scales[sb + 4] >> 4) | ((scales[sb] >> 6) << 4); }
         const uint32_t q4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t + tb * 2048 + (l >> 4) * 1024 + ((sb >> 1) * 16 + r) * 16 + (l & 15));
+        uint32_t h5 = 0;  // Q5_K: the fifth bits of the four weights at bits 8e of h5 (high-bit plane, k_repack_q5k_t16)
+        if (type == NFAI_Q5_K_T16)
+            h5 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t + nblk * 144 + tb * 512 + ((sb >> 1) * 16 + r) * 8 + (l >> 4) * 4) >>
+                 (4 * (sb & 1) + ((l >> 2) & 3));
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             const uint32_t q = (q4 >> (8 * e)) & 0xFFu;
-            out[e] = d * (float)sc * (float)((sb & 1) ? (q >> 4) : (q & 0xF)) - dmin * (float)m;
+            const uint32_t q5 = ((sb & 1) ? (q >> 4) : (q & 0xF)) | (((h5 >> (8 * e)) & 1u) << 4);
+            out[e] = d * (float)sc * (float)q5 - dmin * (float)m;
         }
     } else {  // NFAI_Q6_K_T16: k_embed_q6t
         const uint32_t n = kk >> 7, qd = (kk >> 5) & 3, l = kk & 31, lh = l >> 4, b = l & 15;

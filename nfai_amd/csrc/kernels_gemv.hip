@@ -794,7 +794,7 @@ static hipError_t dispatch_mode(const GemvParams &p, const GemvPlan &pl, int mod
 
 hipError_t launch_gemv(const GemvArgs &a, hipStream_t s)
 {
-    if (is_t16(a.w_type) || a.w_type == NFAI_KQ_MIXED) return launch_gemv_kqm(a, s);
+    if (is_t16(a.w_type) || a.w_type == NFAI_KQ_MIXED || a.w_type == NFAI_KQ_MIXED5) return launch_gemv_kqm(a, s);
     if (a.w_type == NFAI_Q4_K || a.w_type == NFAI_Q6_K) return launch_gemv_kq(a, s);
     GemvParams p{};
     const int rpu = (a.mode == GEMV_QKV_ROPE || a.mode == GEMV_GATEUP) ? 2 : 1;
@@ -997,7 +997,7 @@ const uint16_t *gemv_xcd_calibrate(Ctx *c)
 bool gemv_begin_ok(const GemvArgs &a)
 {
     if (a.mode != GEMV_QKV_ROPE || !a.gamma) return false;
-    if (is_t16(a.w_type) || a.w_type == NFAI_KQ_MIXED) return a.K % 256 == 0;
+    if (is_t16(a.w_type) || a.w_type == NFAI_KQ_MIXED || a.w_type == NFAI_KQ_MIXED5) return a.K % 256 == 0;
     return a.w_type == NFAI_F16 || a.w_type == NFAI_F32;  // both forms of the fp16 / fp32 GEMV carry it
 }
 

@@ -1,6 +1,6 @@
 // kernels_gemv_kqm.hip — decode GEMV on ggml K-quant and Q8_0 weights, second generation: the integer dot products
 // of the quantised weights with fixed-point activations run on the matrix cores (v_mfma_i32_16x16x64_i8 used as
-// 64 independent 16-wide dot products per instruction), the K-quant / Q8_0 scales are applied in fp32.
+// 64 independent 16-wide dot products per instruction), the K-quant / Q8_0 scales are applied in fp32 (K-quants: Q4_K, Q5_K, Q6_K).
 // Same op as kernels_gemv_kq.hip (MatrixMultiplyShader.cs:255-289 on weights the reference cannot
 // load at all, Parser.cs:111-114); that file stays as the path for row counts that are not a
 // multiple of 16.
@@ -25,12 +25,15 @@
 //   Q4_K: plane 0  [tile][blk][h:2][lane:64][16 B]  lane = G*16 + r holds qs[32G+16h .. +16) of row 16*tile+r,
 //                  i.e. lane group G owns sub-blocks 2G (low nibbles) and 2G+1 (high nibbles) of its row;
 //         plane 1  [tile][blk][r:16][16 B]          d, dmin, 12 scale bytes of row 16*tile+r.
+//   Q5_K: planes 0 and 1 of Q4_K (same bytes: qs and the 16-byte header), and
+//         plane 2  [tile][blk][lane:64][8 B]        the 64 fifth bits (qh) of the weights lane (G, r) unpacks, in the order of
+//                                                   q5t_dot (kqm.h): one shift and one v_and_or_b32 per four weights.
 //   Q6_K: see k_repack_q6k_t16.
 //   Q8_0: plane 0  [tile][blk][h:4][lane:64][16 B]  lane = G*16 + r holds qs bytes 64h + 16G .. +16 of super-block blk of
 //                  row 16*tile+r: 16 weights of ONE 32-block (2h + (G >> 1)), so one d per lane and MFMA;
 //         plane 1  [tile][blk][r:16][16 B]          the eight fp16 d of that row and super-block, d of 32-block b at half
 //                                                   (b & 1) * 4 + (b >> 1): lanes of group G read the 8 bytes of their four d.
-// Every wave-wide load is one contiguous kilobyte (quants) or 256 bytes (headers).
+// Every wave-wide load is one contiguous kilobyte (quants), 512 bytes (Q5_K high bits) or 256 bytes (headers).
 //
 // Work split: a workgroup owns whole 16-row tiles ("units": one tile, or the gate and the up tile of
 // the same rows); its waves split K (wave w owns super-blocks w*BPW .. w*BPW+BPW-1 of every tile and
@@ -182,10 +185,13 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
     // QT = NFAI_KQ_MIXED (QKV only): Q4_K and Q6_K segments in one launch (Q4_K_M files keep attn_v in Q6_K on half of
     // the blocks); the activations are staged in both fragment layouts and every step branches on its segment's type.
     // QT = NFAI_Q8_0_T16: its own A-fragment layout, never mixed with the K-quants (llama.hip gives a Q8_0 segment its own launch).
-    constexpr bool HAS8 = QT == NFAI_Q8_0_T16;
-    constexpr bool HAS4 = !HAS8 && QT != NFAI_Q6_K_T16, HAS6 = !HAS8 && QT != NFAI_Q4_K_T16, MIXED = HAS4 && HAS6;
+    // QT = NFAI_Q5_K_T16: the Q4_K staging (fragments and sums of x'); NFAI_KQ_MIXED5: Q5_K and Q6_K segments as NFAI_KQ_MIXED.
+    constexpr bool HAS8 = QT == NFAI_Q8_0_T16, HAS5 = QT == NFAI_Q5_K_T16 || QT == NFAI_KQ_MIXED5;
+    constexpr bool HAS4 = !HAS8 && QT != NFAI_Q6_K_T16, HAS6 = !HAS8 && QT != NFAI_Q4_K_T16 && QT != NFAI_Q5_K_T16, MIXED = HAS4 && HAS6;
     static_assert(!MIXED || MODE == GEMV_QKV_ROPE, "mixed encodings exist for the q|k|v launch only");
-    using Regs = typename std::conditional<QT == NFAI_Q4_K_T16, Q4T, typename std::conditional<HAS8, Q8T, Q6T>::type>::type;
+    using Regs = typename std::conditional<
+        QT == NFAI_Q4_K_T16, Q4T,
+        typename std::conditional<HAS8, Q8T, typename std::conditional<QT == NFAI_Q5_K_T16, Q5T, Q6T>::type>::type>::type;
     constexpr int R = MODE == GEMV_GATEUP ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x, lane = tid & 63, nw = blockDim.x >> 6;
@@ -251,9 +257,14 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
             buf = q6t_load(p, seg, tile, blk, lane);
         } else if constexpr (HAS8) {
             buf = q8t_load(p, seg, tile, blk, lane);
+        } else if constexpr (QT == NFAI_Q5_K_T16) {
+            buf = q5t_load(p, seg, tile, blk, lane);
         } else {
             if ((p.seg6 >> seg) & 1u) {
                 buf = q6t_load(p, seg, tile, blk, lane);
+            } else if constexpr (HAS5) {  // the high bits ride in the first two words of the Q6_K qh slot
+                const Q5T q = q5t_load(p, seg, tile, blk, lane);
+                buf.qla = q.q0; buf.qlb = q.q1; buf.sc = q.hdr; buf.qh[0] = q.qh[0]; buf.qh[1] = q.qh[1];
             } else {
                 const Q4T q = q4t_load(p, seg, tile, blk, lane);
                 buf.qla = q.q0; buf.qlb = q.q1; buf.sc = q.hdr;
@@ -341,6 +352,8 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
                 if constexpr (HAS4) {
                     const f32x4 sm = *reinterpret_cast<const f32x4 *>(sums + (blk * 4 + g) * 4);
                     if constexpr (QT == NFAI_Q4_K_T16) a = q4t_dot(buf, af, f32x2{sm[0], sm[1]}, g);
+                    else if constexpr (QT == NFAI_Q5_K_T16) a = q5t_dot(buf, af, f32x2{sm[0], sm[1]}, g);
+                    else if constexpr (HAS5) a = q5t_dot(Q5T{buf.qla, buf.qlb, buf.sc, u32x2{buf.qh[0], buf.qh[1]}}, af, f32x2{sm[0], sm[1]}, g);
                     else a = q4t_dot(Q4T{buf.qla, buf.qlb, buf.sc}, af, f32x2{sm[0], sm[1]}, g);
                 }
             }
@@ -537,6 +550,68 @@ hipError_t launch_repack_q80_t16(const void *native, void *tiled, uint64_t rows,
     return hipGetLastError();
 }
 
+// ---- Q5_K repack: native 176-byte blocks (row-major: d, dmin, scales[12], qh[32], qs[128]) -> T16 planes -------------------
+// Planes 0 and 1 as k_repack_q4k_t16 (qs at byte 48 of the block, the header is its first 16 bytes).  Plane 2: word hf of lane
+// (G, r) holds, for the weights l = 16hf + 4i + b (b = byte of dword i of q{hf}), bit 2G of qh[l] at 8b + i and bit 2G+1 at 8b + 4 + i.
+__global__ void k_repack_q5k_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
+{
+    const uint64_t tb = blockIdx.x;
+    const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB), t = threadIdx.x;
+    const uint64_t nblk = (uint64_t)n_tiles * 16 * NB;
+    if (t < 128) {
+        const uint32_t h = t >> 6, ln = t & 63, G = ln >> 4, r = ln & 15;
+        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB + blk) * 176 + 48 + 32 * G + 16 * h;
+        *reinterpret_cast<u32x4 *>(dst + tb * 2048 + h * 1024 + ln * 16) = *reinterpret_cast<const u32x4 *>(s);
+    } else if (t < 256) {
+        const uint32_t hf = t & 1, ln = (t - 128) >> 1, G = ln >> 4, r = ln & 15;
+        const uint8_t *blkp = src + ((uint64_t)(tile * 16 + r) * NB + blk) * 176;
+        if (t < 144) *reinterpret_cast<u32x4 *>(dst + nblk * 128 + tb * 256 + (t - 128) * 16) =
+            *reinterpret_cast<const u32x4 *>(src + ((uint64_t)(tile * 16 + (t - 128)) * NB + blk) * 176);
+        const u32x4 qh = *reinterpret_cast<const u32x4 *>(blkp + 16 + 16 * hf);  // qh[16hf .. 16hf + 16)
+        uint32_t word = 0;
+#pragma unroll
+        for (int l = 0; l < 16; l++) {
+            const uint32_t byte = (qh[l >> 2] >> (8 * (l & 3))) & 0xFFu, i = l >> 2, b = l & 3;
+            word |= ((byte >> (2 * G)) & 1u) << (8 * b + i);
+            word |= ((byte >> (2 * G + 1)) & 1u) << (8 * b + 4 + i);
+        }
+        *reinterpret_cast<uint32_t *>(dst + nblk * 144 + tb * 512 + ln * 8 + hf * 4) = word;
+    }
+}
+
+hipError_t launch_repack_q5k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
+{
+    if (rows == 0) return hipSuccess;
+    if (rows % 16 || cols % 256) return hipErrorInvalidValue;
+    const uint64_t nb = cols / 256, grid = rows / 16 * nb;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    k_repack_q5k_t16<<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(native), static_cast<uint8_t *>(tiled), (uint32_t)(rows / 16),
+                                                    (uint32_t)nb);
+    return hipGetLastError();
+}
+
+__global__ void k_embed_q5t(const uint8_t *table, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= E) return;
+    tok += blockIdx.y;
+    y += (uint64_t)blockIdx.y * E;
+    const uint32_t NB = E / 256, blk = k >> 8, kk = k & 255, sb = kk >> 5, l = kk & 31;
+    const uint64_t row = tok[0], tile = row >> 4, r = row & 15, tb = tile * NB + blk, nblk = n_rows * NB;
+    const uint8_t *hdr = table + nblk * 128 + tb * 256 + r * 16;
+    const float d = (float)*reinterpret_cast<const _Float16 *>(hdr), dmin = (float)*reinterpret_cast<const _Float16 *>(hdr + 2);
+    const uint8_t *scales = hdr + 4;
+    uint32_t sc, m;
+    if (sb < 4) { sc = scales[sb] & 63; m = scales[sb + 4] & 63; }
+    else { sc = (scales[sb + 4] & 0xF) | ((scales[sb - 4] >> 6) << 4); m = (scales[sb + 4] >> 4) | ((scales[sb] >> 6) << 4); }
+    const uint32_t ln = (sb >> 1) * 16 + (uint32_t)r;
+    const uint8_t q = table[tb * 2048 + (l >> 4) * 1024 + ln * 16 + (l & 15)];
+    const uint32_t hw = *reinterpret_cast<const uint32_t *>(table + nblk * 144 + tb * 512 + ln * 8 + (l >> 4) * 4);
+    const uint32_t bit = (hw >> (8 * (l & 3) + 4 * (sb & 1) + ((l >> 2) & 3))) & 1u;
+    const float qv = (float)(((sb & 1) ? (q >> 4) : (q & 0xF)) | (bit << 4));
+    y[k] = d * (float)sc * qv - dmin * (float)m;
+}
+
 __global__ void k_embed_q8t(const uint8_t *table, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -596,6 +671,7 @@ hipError_t launch_embed_rows_kqt(const void *table, int type, uint64_t n_rows, c
     if (type == NFAI_Q4_K_T16) k_embed_q4t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
     else if (type == NFAI_Q6_K_T16) k_embed_q6t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
     else if (type == NFAI_Q8_0_T16) k_embed_q8t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
+    else if (type == NFAI_Q5_K_T16) k_embed_q5t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -622,9 +698,11 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
     const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB);
     const uint64_t nblk = (uint64_t)n_tiles * 16 * NB;
     _Float16 *orow = reinterpret_cast<_Float16 *>(stage[threadIdx.x >> 6] + r * DQ_ROW);
-    if constexpr (QT == NFAI_Q4_K_T16) {
+    if constexpr (QT == NFAI_Q4_K_T16 || QT == NFAI_Q5_K_T16) {
         const u32x4 q0 = load_nt16(W + tb * 2048 + lane * 16), q1 = load_nt16(W + tb * 2048 + 1024 + lane * 16);
         const u32x4 hdr = load_nt16(W + nblk * 128 + tb * 256 + r * 16);
+        u32x2 qh5 = {0u, 0u};  // Q5_K: the high-bit plane (bit order of q5t_dot)
+        if constexpr (QT == NFAI_Q5_K_T16) qh5 = *reinterpret_cast<const u32x2 *>(W + nblk * 144 + tb * 512 + lane * 8);
         const float d = h2f_lo(hdr[0]), dmin = h2f_hi(hdr[0]);
 #pragma unroll
         for (int h = 0; h < 2; h++) {
@@ -642,7 +720,9 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
                     const uint32_t byte = ((e < 4 ? wa : wb) >> (8 * (e & 3))) & 0xFFu;
-                    const uint32_t nib = h ? (byte >> 4) : (byte & 0xFu);
+                    uint32_t nib = h ? (byte >> 4) : (byte & 0xFu);
+                    if constexpr (QT == NFAI_Q5_K_T16)  // weight 8c + e: dword 2 (c & 1) + (e >> 2) of q{c >> 1}
+                        nib |= ((qh5[c >> 1] >> (8 * (e & 3) + 4 * h + 2 * (c & 1) + (e >> 2))) & 1u) << 4;
                     o[e] = (_Float16)(d1 * (float)nib - m1);
                 }
                 *reinterpret_cast<f16x8 *>(orow + sb * 32 + c * 8) = o;
@@ -711,6 +791,8 @@ hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64
         k_dequant_t16<NFAI_Q4_K_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
     else if (type == NFAI_Q6_K_T16)
         k_dequant_t16<NFAI_Q6_K_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
+    else if (type == NFAI_Q5_K_T16)
+        k_dequant_t16<NFAI_Q5_K_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
     else if (type == NFAI_Q8_0_T16)
         k_dequant_t16<NFAI_Q8_0_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
     else return hipErrorInvalidValue;
@@ -768,8 +850,8 @@ static hipError_t q4t_bpw(const KqmParams &p, int bpw, uint32_t grid, uint32_t b
 
 hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s)
 {
-    if (a.w_type != NFAI_Q4_K_T16 && a.w_type != NFAI_Q6_K_T16 && a.w_type != NFAI_Q8_0_T16 && a.w_type != NFAI_KQ_MIXED) return hipErrorInvalidValue;
-    if (a.w_type == NFAI_KQ_MIXED && a.mode != GEMV_QKV_ROPE) return hipErrorInvalidValue;
+    if (!is_t16(a.w_type) && a.w_type != NFAI_KQ_MIXED && a.w_type != NFAI_KQ_MIXED5) return hipErrorInvalidValue;
+    if ((a.w_type == NFAI_KQ_MIXED || a.w_type == NFAI_KQ_MIXED5) && a.mode != GEMV_QKV_ROPE) return hipErrorInvalidValue;
     if (a.K == 0 || a.K % 256 != 0 || a.K > 32768) return hipErrorInvalidValue;
     KqmParams p{};
     uint32_t total_tiles = 0;
@@ -834,7 +916,7 @@ hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s)
     }
     p.UB = min((uint32_t)max(1, min(env_ub, 8)), min(upb, nw));
     const int R = a.mode == GEMV_GATEUP ? 2 : 1;
-    const size_t nlay = a.w_type == NFAI_KQ_MIXED ? 2 : 1;  // fragment layouts staged
+    const size_t nlay = (a.w_type == NFAI_KQ_MIXED || a.w_type == NFAI_KQ_MIXED5) ? 2 : 1;  // fragment layouts staged
     auto lds_bytes = [&](uint32_t ub) {
         return nlay * ((size_t)nw * bpw * 1024 + (size_t)nw * bpw * 64) + (size_t)nw * bpw * 4 + (size_t)2 * ub * R * nw * 256 + 128 + 192 + BEGIN_CS_WORDS * 4;  // + 48 words of the fused ArgMax + the cos/sin table of a token's first launch
     };
@@ -846,7 +928,15 @@ hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s)
         NFAI_STAMP_SET(p, names[a.mode & 3], grid, nw * 64);
     }
     if (a.w_type == NFAI_KQ_MIXED) return q4t_bpw<NFAI_KQ_MIXED, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
-    if (a.w_type == NFAI_Q8_0_T16) {
+    if (a.w_type == NFAI_KQ_MIXED5) return q4t_bpw<NFAI_KQ_MIXED5, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
+    if (a.w_type == NFAI_Q5_K_T16) {
+        switch (a.mode) {
+            case GEMV_PLAIN: return q4t_bpw<NFAI_Q5_K_T16, GEMV_PLAIN>(p, bpw, grid, nw * 64, lds, s);
+            case GEMV_RESIDUAL: return q4t_bpw<NFAI_Q5_K_T16, GEMV_RESIDUAL>(p, bpw, grid, nw * 64, lds, s);
+            case GEMV_QKV_ROPE: return q4t_bpw<NFAI_Q5_K_T16, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
+            case GEMV_GATEUP: return q4t_bpw<NFAI_Q5_K_T16, GEMV_GATEUP>(p, bpw, grid, nw * 64, lds, s);
+        }
+    } else if (a.w_type == NFAI_Q8_0_T16) {
         switch (a.mode) {
             case GEMV_PLAIN: return q4t_bpw<NFAI_Q8_0_T16, GEMV_PLAIN>(p, bpw, grid, nw * 64, lds, s);
             case GEMV_RESIDUAL: return q4t_bpw<NFAI_Q8_0_T16, GEMV_RESIDUAL>(p, bpw, grid, nw * 64, lds, s);

@@ -21,7 +21,7 @@ struct KqmParams {
     const float *gamma;
     float eps;
     uint32_t K, NB, NU, UB;
-    uint32_t seg6;             // NFAI_KQ_MIXED: bit i set = segment i is Q6_K (else Q4_K)
+    uint32_t seg6;             // NFAI_KQ_MIXED(5): bit i set = segment i is Q6_K (else Q4_K, or Q5_K for NFAI_KQ_MIXED5)
     uint32_t rot;              // q|k|v: unit u works on tile (u + rot) mod NU
     float *y;
     const float *res;
@@ -38,6 +38,7 @@ struct KqmParams {
 
 struct Q4T { u32x4 q0, q1, hdr; };
 struct Q8T { u32x4 q[4]; u32x2 d; };
+struct Q5T { u32x4 q0, q1, hdr; u32x2 qh; };
 
 __device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t mask, uint32_t bits) { return (a & mask) | bits; }
 
@@ -138,9 +139,70 @@ __device__ __forceinline__ float q4t_dot(const Q4T &w, const i32x4 (&af)[4], f32
     return a;
 }
 
+// One step of a wave on a Q5_K T16 tensor: the Q4_K planes (low nibbles, headers) plus the high-bit plane, 8 bytes per lane: one
+// contiguous 512-byte load per wave (14 VGPRs per step).
+__device__ __forceinline__ Q5T q5t_load_raw(const uint8_t *base, uint64_t n_tiles, uint32_t NB, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    const uint64_t tb = (uint64_t)tile * NB + blk;
+    const uint64_t nblk = n_tiles * 16 * NB;
+    Q5T r;
+    r.q0 = load_nt16(base + tb * 2048 + lane * 16);
+    r.q1 = load_nt16(base + tb * 2048 + 1024 + lane * 16);
+    r.hdr = load_nt16(base + nblk * 128 + tb * 256 + (lane & 15) * 16);
+    r.qh = __builtin_nontemporal_load((const GLOBAL_AS u32x2 *)(base + nblk * 144 + tb * 512 + lane * 8));
+    return r;
+}
+
+__device__ __forceinline__ Q5T q5t_load(const KqmParams &p, uint32_t seg, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    return q5t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
+}
+
+// q4t_dot with the fifth bit of every weight: q = nibble | bit << 4 (0..31, still a non-negative byte operand).  Word hf of w.qh holds
+// the bits of the 32 weights of q{hf}: weight byte b of dword i at bit 8b + i (low nibbles, sub-block 2G) and 8b + 4 + i (high nibbles,
+// sub-block 2G+1), so each dword of four weights takes one shift and one v_and_or_b32 onto its masked nibbles.
+__device__ __forceinline__ float q5t_dot(const Q5T &w, const i32x4 (&af)[4], f32x2 sums, uint32_t g)
+{
+    constexpr uint32_t M = 0x0F0F0F0Fu, B = 0x10101010u;
+    i32x4 dlo = {0, 0, 0, 0}, dhi = {0, 0, 0, 0};
+#pragma unroll
+    for (int hf = 0; hf < 2; hf++) {
+        const u32x4 q = hf ? w.q1 : w.q0;
+        const uint32_t h = w.qh[hf];
+        u32x4 blo, bhi;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            blo[i] = and_or(h << (4 - i), B, q[i] & M);
+            bhi[i] = and_or(h >> i, B, (q[i] >> 4) & M);
+        }
+        dlo = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[0 * 2 + hf], __builtin_bit_cast(i32x4, blo), dlo, 0, 0, 0);
+        dhi = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[1 * 2 + hf], __builtin_bit_cast(i32x4, bhi), dhi, 0, 0, 0);
+    }
+    // the Q4_K epilogue: get_scale_min_k4 of sub-blocks 2G and 2G+1, d * sc * sum q x' - dmin * m * sum x'
+    const float d = h2f_lo(w.hdr[0]), dmin = h2f_hi(w.hdr[0]);
+    float scv[2], mv[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const uint32_t sb = 2 * g + h, sh = (sb & 3) * 8;
+        const uint32_t lo8 = (w.hdr[1] >> sh) & 0xFFu, mid = (w.hdr[2] >> sh) & 0xFFu, hi8 = (w.hdr[3] >> sh) & 0xFFu;
+        const bool low = sb < 4;
+        const uint32_t sc = low ? (lo8 & 63u) : ((hi8 & 0xFu) | ((lo8 >> 6) << 4));
+        const uint32_t mn = low ? (mid & 63u) : ((hi8 >> 4) | ((mid >> 6) << 4));
+        scv[h] = d * (float)sc;
+        mv[h] = dmin * (float)mn;
+    }
+    const float vlo = fmaf((float)dlo[2], 65536.0f, fmaf((float)dlo[1], 256.0f, (float)dlo[0]));
+    const float vhi = fmaf((float)dhi[2], 65536.0f, fmaf((float)dhi[1], 256.0f, (float)dhi[0]));
+    float a = scv[0] * vlo;
+    a = fmaf(-mv[0], sums[0], a);
+    a = fmaf(scv[1], vhi, a);
+    a = fmaf(-mv[1], sums[1], a);
+    return a;
+}
+
 // Fixed-point staging of ONE 256-element super-block of the activation vector by one wave (lane holds elements 4*lane .. +3, after the
 // optional RMSNorm): power-of-two scale so that |x * 2^S| < 2^22, three signed base-256 digits per element written as MFMA A
-// fragments [blk][slot:4][G][digit][16 B] (Q4_K layout in xa, Q6_K layout in xa6, Q8_0 layout in xa), the sums of x' per scale group
+// fragments [blk][slot:4][G][digit][16 B] (Q4_K / Q5_K layout in xa, Q6_K layout in xa6, Q8_0 layout in xa), the sums of x' per scale group
 // (K-quants only) and 2^-S.  Nothing written here is read by another wave.
 template <bool HAS4, bool HAS6, bool HAS8 = false>
 __device__ __forceinline__ void kqm_stage(const f32x4 v, const uint32_t blk, const uint32_t lane, uint8_t *xa, uint8_t *xa6, float *sums,

@@ -51,9 +51,9 @@ struct WideShadow {
     ~WideShadow() { if (ptr) hipFree(ptr); }
 };
 
-// Does the MFMA prefill widen a matrix of this type to fp16?  Every quantised one; under NFAI_PREFILL_FUSED=1 (the K-quants take
-// the dequant-in-LDS GEMM) only Q8_0, which has no such GEMM.
-static bool prefill_widens(int type, bool fused) { return type != NFAI_F16 && (!fused || type == NFAI_Q8_0_T16); }
+// Does the MFMA prefill widen a matrix of this type to fp16?  Every quantised one; under NFAI_PREFILL_FUSED=1 (Q4_K / Q6_K take
+// the dequant-in-LDS GEMM) only Q8_0 and Q5_K, which have no such GEMM.
+static bool prefill_widens(int type, bool fused) { return type != NFAI_F16 && (!fused || type == NFAI_Q8_0_T16 || type == NFAI_Q5_K_T16); }
 
 enum KClass { KC_QKV = 0, KC_ATTN = 1, KC_WO = 2, KC_GATEUP = 3, KC_DOWN = 4, KC_LMHEAD = 5, KC_OTHER = 6, KC_ENGINE = 7, KC_N = 8 };
 
@@ -188,7 +188,7 @@ int check_shape(const char *what, const Tensor &t, uint64_t rows, uint64_t cols,
                     (unsigned long long)t.cols, (unsigned long long)rows, (unsigned long long)cols);
     if (!matrix && t.type != NFAI_F32) return fail(NFAI_ERR_UNSUPPORTED, "finalize: norm gain %s must be F32 (type %d)", what, t.type);
     if (matrix && t.type != NFAI_F16 && t.type != NFAI_F32 && !is_kquant(t.type))
-        return fail(NFAI_ERR_UNSUPPORTED, "finalize: matrix %s has ggml type %d; kernels exist for F16/F32/Q4_K/Q6_K/Q8_0", what, t.type);
+        return fail(NFAI_ERR_UNSUPPORTED, "finalize: matrix %s has ggml type %d; kernels exist for F16/F32/Q4_K/Q5_K/Q6_K/Q8_0", what, t.type);
     return NFAI_OK;
 }
 
@@ -339,18 +339,29 @@ GemvArgs gemv_base(Model *m, const Tensor &w, const float *x, uint32_t K)
 // [RMSNorm + Wq, Wk, Wv + RoPE + KV write] of block L on the activation vector x (TransformerBlock.cs:129-141).
 // One launch when q, k, v share an encoding; Q4_K_M files keep attn_v in Q6_K on some blocks: then the segments that differ get
 // their own launch (same kernel family, same epilogue).  A Q8_0 segment is never mixed with K-quant segments: it shares a launch only
-// with other Q8_0 segments.  qkv_launch: the launch that starts at segment `first` (-> `last`).
+// with other Q8_0 segments.  Q5_K_M files keep attn_v in Q6_K the same way: Q5_K and Q6_K segments share a launch (NFAI_KQ_MIXED5);
+// Q4_K and Q5_K segments never do.  qkv_launch: the launch that starts at segment `first` (-> `last`).
 GemvArgs qkv_launch(Model *m, Layer &L, const float *x, int first, int &last)
 {
     const nfai_llama_desc &d = m->d;
     const Tensor *seg[3] = {&L.wq, &L.wk, &L.wv};
     auto t16 = [](int ty) { return ty == NFAI_Q4_K_T16 || ty == NFAI_Q6_K_T16; };  // the K-quants of the mixed kernel
+    auto t16q5 = [](int ty) { return ty == NFAI_Q5_K_T16 || ty == NFAI_Q6_K_T16; };  // ... of its Q5_K form
     last = first;
-    // segments of one encoding share a launch; so do T16 Q4_K and Q6_K segments (mixed kernel, kernels_gemv_kqm.hip)
-    while (last + 1 < 3 && (seg[last + 1]->type == seg[first]->type || (t16(seg[last + 1]->type) && t16(seg[first]->type)))) last++;
+    // segments of one encoding share a launch; so do T16 Q4_K and Q6_K segments (mixed kernel, kernels_gemv_kqm.hip), and T16 Q5_K and
+    // Q6_K segments.  `fam`: the family the launch has committed to (0 none yet, 4 or 5 once it holds a Q4_K or a Q5_K segment).
+    int fam = seg[first]->type == NFAI_Q4_K_T16 ? 4 : (seg[first]->type == NFAI_Q5_K_T16 ? 5 : 0);
+    while (last + 1 < 3) {
+        const int nt = seg[last + 1]->type, ft = seg[first]->type;
+        const int nfam = nt == NFAI_Q4_K_T16 ? 4 : (nt == NFAI_Q5_K_T16 ? 5 : 0);
+        const bool joins = nt == ft || (t16(nt) && t16(ft) && fam != 5 && nfam != 5) || (t16q5(nt) && t16q5(ft) && fam != 4 && nfam != 4);
+        if (!joins) break;
+        if (nfam) fam = nfam;
+        last++;
+    }
     GemvArgs a = gemv_base(m, *seg[first], x, d.E);
     for (int i = first; i <= last; i++) {
-        if (seg[i]->type != seg[first]->type) a.w_type = NFAI_KQ_MIXED;
+        if (seg[i]->type != seg[first]->type) a.w_type = fam == 5 ? NFAI_KQ_MIXED5 : NFAI_KQ_MIXED;
         if (seg[i]->type == NFAI_Q6_K_T16) a.seg6_mask |= 1u << i;
     }
     for (int i = 0; i < 3; i++) {
@@ -859,14 +870,14 @@ static int set_tensor_impl(Model *m, const char *name, int type, uint64_t rows, 
     Tensor nt;
     nt.type = type; nt.rows = rows; nt.cols = cols; nt.bytes = rb * rows;
     hipStream_t s = m->ctx->stream;
-    if (type == NFAI_Q8_0 && (rows == 0 || rows % 16))
-        return fail(NFAI_ERR_UNSUPPORTED, "set_tensor(%s): Q8_0 needs rows %% 16 == 0, cols %% 256 == 0 and cols <= 32768 (%llu x %llu)", name,
-                    (unsigned long long)rows, (unsigned long long)cols);
+    if ((type == NFAI_Q8_0 || type == NFAI_Q5_K) && (rows == 0 || rows % 16))
+        return fail(NFAI_ERR_UNSUPPORTED, "set_tensor(%s): %s needs rows %% 16 == 0, cols %% 256 == 0 and cols <= 32768 (%llu x %llu)", name,
+                    type == NFAI_Q8_0 ? "Q8_0" : "Q5_K", (unsigned long long)rows, (unsigned long long)cols);
     const bool q4_t16 = type == NFAI_Q4_K && rows > 0 && rows % 16 == 0, q6_t16 = type == NFAI_Q6_K && rows > 0 && rows % 16 == 0;
-    const bool q8_t16 = type == NFAI_Q8_0;
+    const bool q8_t16 = type == NFAI_Q8_0, q5_t16 = type == NFAI_Q5_K;
     auto fail_free = [&](void *a, void *b, int rc) { if (a) hipFree(a); if (b) hipFree(b); return rc; };
-    if (type == NFAI_Q6_K || q4_t16 || q8_t16) {
-        // native blocks (host or device) -> owned repacked copy: Q6_K planes (common.h), Q4_K / Q6_K / Q8_0 T16 tiles (kernels_gemv_kqm.hip)
+    if (type == NFAI_Q6_K || q4_t16 || q8_t16 || q5_t16) {
+        // native blocks (host or device) -> owned repacked copy: Q6_K planes (common.h), Q4_K / Q5_K / Q6_K / Q8_0 T16 tiles (kernels_gemv_kqm.hip)
         void *native = dev, *staged = nullptr;
         if (!dev) {
             int rc = dalloc(&staged, nt.bytes, s);
@@ -881,12 +892,14 @@ static int set_tensor_impl(Model *m, const char *name, int type, uint64_t rows, 
         hipError_t e = q4_t16 ? launch_repack_q4k_t16(native, nt.ptr, rows, cols, s)
                      : q6_t16 ? launch_repack_q6k_t16(native, nt.ptr, rows, cols, s)
                      : q8_t16 ? launch_repack_q80_t16(native, nt.ptr, rows, cols, s)
+                     : q5_t16 ? launch_repack_q5k_t16(native, nt.ptr, rows, cols, s)
                               : launch_repack_q6k(native, nt.ptr, rows * cols / 256, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return fail_free(staged, nt.ptr, fail(NFAI_ERR_HIP, "set_tensor(%s): K-quant repack failed: %s", name, hipGetErrorString(e)));
         if (q4_t16) nt.type = NFAI_Q4_K_T16;
         if (q6_t16) nt.type = NFAI_Q6_K_T16;
         if (q8_t16) nt.type = NFAI_Q8_0_T16;
+        if (q5_t16) nt.type = NFAI_Q5_K_T16;
         if (staged) hipFree(staged);
     } else if (dev) {
         nt.ptr = dev;
@@ -1312,7 +1325,7 @@ static int prefill_chunk(Model *m, const uint32_t *tokens, uint32_t T, const flo
     for (Layer &Lq : m->layers) {
         Layer L = Lq;
         WideShadow &wd = *w.wide;
-        if (wd.ptr) {   // (NFAI_PREFILL_FUSED=1: allocated only for Q8_0 matrices, ensure_wide_shadow)
+        if (wd.ptr) {   // (NFAI_PREFILL_FUSED=1: allocated only for Q8_0 / Q5_K matrices, ensure_wide_shadow)
             const size_t li = (size_t)(&Lq - m->layers.data());
             const bool kept = wd.all && wd.done[li];  // widened by an earlier chunk / prefill and still current
             uint64_t off = wd.all ? li * wd.slot : 0;

@@ -30,7 +30,7 @@ class ModelOptions:
 
 @dataclass
 class QuantTensor:
-    """A GGUF tensor kept in its on-disk block encoding (Q4_K / Q6_K / Q8_0): raw bytes + logical shape."""
+    """A GGUF tensor kept in its on-disk block encoding (Q4_K / Q5_K / Q6_K / Q8_0): raw bytes + logical shape."""
     data: np.ndarray  # uint8
     ggml_type: int
     shape: tuple  # (rows, cols) = (ne1, ne0)

@@ -91,6 +91,64 @@ def quantize_q8_0(W) -> bytes:
     return out.tobytes()
 
 
+def _f16_up(v):
+    """The smallest fp16 values >= v (v >= 0, float32 array): a scale that a 6-bit code times it must still reach v."""
+    h = np.asarray(v, np.float32).astype(np.float16)
+    return np.where(h.astype(np.float32) < v, np.nextafter(h, np.float16(np.inf)), h).astype(np.float16)
+
+
+def quantize_q5_k(W) -> bytes:
+    """Valid ggml block_q5_K for every row of W [rows][cols] (cols % 256 == 0): 176 bytes per 256 weights, in the order fp16 d,
+    fp16 dmin, 12 bytes of 6-bit scales / mins (get_scale_min_k4 packing), qh[32], qs[128]; weight = d * sc * q - dmin * m,
+    q = 0..31.  Not llama.cpp's search: per sub-block of 32 the 6-bit min m is rounded up (dmin * m >= -min(x, 0)), then the
+    6-bit scale up (the 31st code reaches max(x)), so every weight is within half a step d * sc of its code."""
+    x = np.asarray(W, dtype=np.float32).reshape(-1, 8, 32)
+    nb = x.shape[0]
+    sub_min = np.maximum(-x.min(axis=2), 0).astype(np.float32)                  # [nb][8]
+    dmin = _f16_up(sub_min.max(axis=1) / np.float32(63))                       # [nb]
+    dm32 = dmin.astype(np.float32)
+    m = np.where(dm32[:, None] > 0, np.ceil(sub_min / np.where(dm32 > 0, dm32, 1)[:, None]), 0).astype(np.int64)
+    m = np.clip(m, 0, 63)
+    off = dm32[:, None] * m.astype(np.float32)                                  # dmin * m, exactly as the decoder forms it
+    need = np.maximum(x.max(axis=2) + off, 0) / np.float32(31)                  # step that reaches max(x) at code 31
+    d = _f16_up(need.max(axis=1) / np.float32(63))
+    d32 = d.astype(np.float32)
+    sc = np.where(d32[:, None] > 0, np.ceil(need / np.where(d32 > 0, d32, 1)[:, None]), 0).astype(np.int64)
+    sc = np.clip(sc, 0, 63)
+    step = d32[:, None] * sc.astype(np.float32)
+    q = np.where(step[:, :, None] > 0, np.rint((x + off[:, :, None]) / np.where(step > 0, step, 1)[:, :, None]), 0)
+    q = np.clip(q, 0, 31).astype(np.uint8)                                      # [nb][8][32]
+    out = np.zeros((nb, 176), np.uint8)
+    out[:, 0:2] = d.view(np.uint8).reshape(nb, 2)
+    out[:, 2:4] = dmin.view(np.uint8).reshape(nb, 2)
+    sc8, m8 = sc.astype(np.uint8), m.astype(np.uint8)
+    # get_scale_min_k4: j < 4: scales[j] = sc, scales[j + 4] = m (6 bits each); j >= 4: low nibbles in scales[j + 4], the two high
+    # bits in the top bits of scales[j - 4] (sc) and scales[j] (m)
+    out[:, 4:8] = sc8[:, :4] | ((sc8[:, 4:] >> 4) << 6)
+    out[:, 8:12] = m8[:, :4] | ((m8[:, 4:] >> 4) << 6)
+    out[:, 12:16] = (sc8[:, 4:] & 0xF) | ((m8[:, 4:] & 0xF) << 4)
+    # pair n = sub-blocks 2n, 2n+1: qs[32n + l] = low nibble of q[2n][l] | high nibble of q[2n+1][l]; fifth bits: qh[l] bit 2n, 2n+1
+    qh = np.zeros((nb, 32), np.uint8)
+    for n in range(4):
+        lo, hi = q[:, 2 * n], q[:, 2 * n + 1]
+        out[:, 48 + 32 * n:80 + 32 * n] = (lo & 0xF) | ((hi & 0xF) << 4)
+        qh |= ((lo >> 4) << (2 * n)) | ((hi >> 4) << (2 * n + 1))
+    out[:, 16:48] = qh
+    return out.tobytes()
+
+
+def q5_k_m_type(name: str, dims, layer_offset: int = 0, n_layers_file: int | None = None) -> int:
+    """ggml type of a matrix in a Q5_K_M file (llama.cpp's mix): Q5_K (13), except Q6_K (14) for attn_v / ffn_down of the
+    use_more_bits blocks (bench.use_more_bits) and for the lm_head (output.weight, or a tied token_embd); an untied token_embd is
+    Q5_K."""
+    from bench import use_more_bits
+    if name == "output.weight" or (name == "token_embd.weight" and dims.tied):
+        return 14
+    if name.startswith("blk.") and name.endswith(("attn_v.weight", "ffn_down.weight")):
+        return 14 if use_more_bits(int(name.split(".")[1]) + layer_offset, n_layers_file or dims.L) else 13
+    return 13
+
+
 def make_tokens(dims: LlamaDims, n: int, seed: int = 99) -> np.ndarray:
     rng = np.random.Generator(np.random.PCG64(seed))
     return rng.integers(0, dims.V, size=n, dtype=np.uint32)
