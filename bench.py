@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — decode tokens/s of the HIP Llama-3 path on MI355X, with roofline and CPU baseline.
 
-    python bench.py --gpus 1 --steps 128 --warmup 8            (default: N=1, finishes in minutes)
+    python bench.py --gpus 1 --steps 128 --warmup 8            (the headline only: set-up, context, warm-up, timed steps)
+    python bench.py --gpus 1 --steps 128 --warmup 8 --full     (also everything else: see below; finishes in minutes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus 1 --steps 128 --warmup 8 --dump-outputs DIR   (also writes the last timed step's logits / token)
+
+A plain run does only what `value` needs: it generates the weights, builds the model, fills the context (one MFMA prefill),
+warms up, times the steps, dumps the outputs if asked and prints the line.  `--full` adds, around the same timed region: the
+CPU baseline with its parity comparison, the prefill's check against the decode path and its timed shots, the per-kernel
+roofline, the short-context and host-loop figures, and the other BASELINE configurations (`configs[]`, child processes; for
+N > 1 config 5 over the same stages).  Both runs build the same model and time the same steps on the same inputs.
 
 Workload (BASELINE.json metric "decode tokens/sec Llama-3.2-3B batch=1"): Llama-3.2-3B, fp16 GGUF
 weights kept fp16 in HBM, fp32 activations and fp32 KV cache (the reference's precision), batch-1
@@ -42,6 +49,9 @@ def parse():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--model", default="llama-3.2-3b")
     ap.add_argument("--context", type=int, default=CONTEXT)
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure and check everything else (CPU baseline and parity, prefill "
+                                                        "check and timing, roofline per kernel, short context, host loops, configs[]); --no-cpu-baseline, "
+                                                        "--cpu-tokens, --sample-tokens, --profile-steps, --configs and --pp-configs take effect only with it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-tokens", type=int, default=0, help="tokens of the CPU baseline sample (0 = auto)")
     ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m"], help="GGUF file type of the synthetic weights")
@@ -52,11 +62,11 @@ def parse():
     ap.add_argument("--engine", type=int, default=-1, help="1 / 0: one weight-streaming engine launch per block / the five-launch path (-1 = library default)")
     ap.add_argument("--stage-blocks", default="", help="B0:B1 = run only blocks [B0, B1) of the model (+ embedding + lm_head) as a one-process model: "
                                                         "the per-GPU share of a layer pipeline (BASELINE config 5); tensor types follow the global block index")
-    ap.add_argument("--configs", default="auto", help="auto: the default N=1 run appends BASELINE configs 4 (3B Q4_K_M), 2 (1B fp16) and 5's per-GPU share (8B Q4_K_M, "
+    ap.add_argument("--configs", default="auto", help="auto: the default N=1 run with --full appends BASELINE configs 4 (3B Q4_K_M), 2 (1B fp16) and 5's per-GPU share (8B Q4_K_M, "
                                                       "4 blocks + lm_head) as `configs[]`, each measured in a fresh child process; none: only the headline workload")
-    ap.add_argument("--pp-configs", default="auto", help="N > 1: auto = BASELINE config 5 (Llama-3.1-8B Q4_K_M over the same N stages) follows the headline "
-                                                         "entry as configs[0]; none = only the headline")
-    ap.add_argument("--child", action="store_true", help="(internal) one `configs[]` entry: compact object, bounded CPU work")
+    ap.add_argument("--pp-configs", default="auto", help="N > 1 with --full: auto = BASELINE config 5 (Llama-3.1-8B Q4_K_M over the same N stages) follows "
+                                                         "the headline entry as configs[0]; none = only the headline")
+    ap.add_argument("--child", action="store_true", help="(internal, with --full) one `configs[]` entry: compact object, bounded CPU work")
     ap.add_argument("--sample-tokens", type=int, default=64, help="tokens of the sampling-path (decode_topk + host nucleus) and blocking-greedy timings (0 = skip)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (logits.npy: float32 [V]; token.npy: the greedy token as "
@@ -272,6 +282,7 @@ def run_single(args):
     torch.cuda.set_device(0)
     weights = gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant=args.quant, layer_offset=layer_offset, n_layers_file=n_layers_file)
     mgr = HipBufferManager(0)
+    # the KV capacity leaves room for the CPU comparison's positions in every run, so that a plain run builds the model --full does
     n_cmp = 0 if args.no_cpu_baseline else (args.cpu_tokens or 128)  # ~10-15 s of CPU work on the box's 16 host threads at 3B fp16
     C = max(args.context + args.warmup + args.steps, n_cmp + 1, 16 + args.warmup + args.steps)
     m = LlamaModel(mgr, synth.make_metadata(dims), as_model_tensors(_lib, weights), C,
@@ -282,7 +293,7 @@ def run_single(args):
     # positions 0..n_cmp-1 with logits, greedy: the parity side of the CPU baseline at full size — EVERY token the oracle computes
     # is compared (multi-position attention through all blocks), not only token 0
     gpu_logits, gpu_tokens, tok = [], [], first_token
-    for _ in range(n_cmp):
+    for _ in range(n_cmp if args.full else 0):
         lg, tok = m.Step(tok)
         gpu_logits.append(lg)
         gpu_tokens.append(tok)
@@ -293,7 +304,9 @@ def run_single(args):
     prefill = None
     prompt = synth.make_tokens(dims, args.context, seed=99)
     prompt[0] = first_token
-    if not args.no_mfma_prefill:
+    if not args.no_mfma_prefill and not args.full:
+        m.Prefill(prompt, want_logits=False)          # the context (and first token) that --full's last timed shot leaves
+    elif not args.no_mfma_prefill:
         # parity side-check of the MFMA prefill at the benchmark's own size: the same prompt through the decode path token by
         # token (the reference's way, LlamaModel.cs:103-126) must give the same argmax and logits within the fp16 tolerance
         m.SetToken(int(prompt[0]))
@@ -359,9 +372,30 @@ def run_single(args):
         dump_outputs(args.dump_outputs, {"logits": m.Read(4, dims.V), "token": toks.astype(np.float64)})
     ms_per_step = ev_ms / args.steps
     value = args.steps / (ev_ms / 1e3)
-    # ---- roofline: dominant kernel = the fused RMSNorm + Wgate/Wup GEMV + SiLU*up launch
     pos_mid = pos0 + args.steps // 2
     b_tok, dom_bytes = m.BytesPerToken(pos_mid)
+    workload = (f"{dims.name} {'fp16-GGUF weights (fp16 in HBM)' if args.quant == 'f16' else 'Q4_K_M-GGUF weights (native K-quant blocks in HBM)'}, fp32 activations + {'fp16' if args.kv_f16 else 'fp32'} KV, "
+                f"batch-1 greedy decode of {args.steps} tokens after a {args.context}-token context" + stage_note)
+    out = {
+        "metric": "decode tokens/sec Llama-3.2-3B batch=1; achieved HBM GB/s vs roofline",
+        "value": value, "unit": "tokens/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": workload,
+                   "positions": [pos0, pos0 + args.steps - 1], "kv_capacity": C, "parallelism": "single",
+                   "graph": not args.no_graph,
+                   "xcd_row_shares": dict(zip(("shares", "probe_us_equal_shares"), mgr.XcdShares()))},
+        "token_hbm_gbps": b_tok / (ms_per_step * 1e-3) / 1e9,
+        "token_hbm_frac_of_peak": b_tok / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+        "token_hbm_frac_of_measured_ceiling": b_tok / (ms_per_step * 1e-3) / 1e9 / HBM_MEASURED_CEILING_GBPS,
+        "bytes_per_token": b_tok,
+        "host_wall_ms_per_step": 1e3 * wall / args.steps,
+    }
+    if not args.full:
+        out["wall_s"] = time.perf_counter() - t_start
+        m.Dispose()
+        return out, weights
+    # ---- roofline: dominant kernel = the fused RMSNorm + Wgate/Wup GEMV + SiLU*up launch
     prof = {}
     for _ in range(args.profile_steps):
         if m.Pos >= C:
@@ -425,18 +459,9 @@ def run_single(args):
             kernels.append({"class": label, "what": _CLASS_NAME[label], "launches_per_token": n_launch, "bytes_per_launch": int(nbytes),
                             "us_per_launch": round(us, 3), "gbps": round(nbytes / us / 1e3, 1), "frac": round(nbytes / us / 1e3 / HBM_PEAK_GBPS, 4),
                             "frac_of_measured_ceiling": round(nbytes / us / 1e3 / HBM_MEASURED_CEILING_GBPS, 4)})
-    workload = (f"{dims.name} {'fp16-GGUF weights (fp16 in HBM)' if args.quant == 'f16' else 'Q4_K_M-GGUF weights (native K-quant blocks in HBM)'}, fp32 activations + {'fp16' if args.kv_f16 else 'fp32'} KV, "
-                f"batch-1 greedy decode of {args.steps} tokens after a {args.context}-token context" + stage_note)
-    out = {
-        "metric": "decode tokens/sec Llama-3.2-3B batch=1; achieved HBM GB/s vs roofline",
-        "value": value, "unit": "tokens/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": workload,
-                   "positions": [pos0, pos0 + args.steps - 1], "kv_capacity": C, "parallelism": "single",
-                   "graph": not args.no_graph, "launches_per_block": 2 if engine_on else (4 if args.quant == "f16" else 5),
-                   "launches_per_token": (sum(v[1] for v in prof.values()) // max(1, args.profile_steps)) if prof else None,
-                   "xcd_row_shares": dict(zip(("shares", "probe_us_equal_shares"), mgr.XcdShares()))},
+    out["config"].update({"launches_per_block": 2 if engine_on else (4 if args.quant == "f16" else 5),
+                          "launches_per_token": (sum(v[1] for v in prof.values()) // max(1, args.profile_steps)) if prof else None})
+    out.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBPS, "frac_of_measured_ceiling": achieved / HBM_MEASURED_CEILING_GBPS,
                      "measured_ceiling": HBM_MEASURED_CEILING_GBPS,
@@ -447,14 +472,9 @@ def run_single(args):
                      "bytes_per_launch": dom_bytes, "us_per_launch": gu_ms * 1e3, "us_per_launch_eager_event_pair": gu_eager_ms * 1e3,
                      "timing": "hipEvents on the launch stream around 4 rounds of the kernel's launches of one step (one per block), back to back",
                      "kernels": kernels},
-        "token_hbm_gbps": b_tok / (ms_per_step * 1e-3) / 1e9,
-        "token_hbm_frac_of_peak": b_tok / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-        "token_hbm_frac_of_measured_ceiling": b_tok / (ms_per_step * 1e-3) / 1e9 / HBM_MEASURED_CEILING_GBPS,
-        "bytes_per_token": b_tok,
         "kernel_us_eager_events": per_kernel_us,
-        "host_wall_ms_per_step": 1e3 * wall / args.steps,
         "prefill": prefill,
-    }
+    })
     # ---- the same decode at a SHORT context (positions 16..): the like-for-like figure for per-layer comparisons (MI355X guide: 1B layer)
     m.Reset()
     m.SetToken(first_token)
@@ -529,7 +549,7 @@ def run_child_configs(args):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     entries = []
     for label, extra in CHILD_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--configs", "none", "--gpus", "1", "--steps", "64", "--warmup", "8",
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--full", "--configs", "none", "--gpus", "1", "--steps", "64", "--warmup", "8",
                "--context", str(args.context), "--sample-tokens", "0", "--profile-steps", "3"] + extra
         t0 = time.perf_counter()
         try:
@@ -573,12 +593,14 @@ def main():
         sys.exit(subprocess.run(cmd).returncode)
     if args.gpus > 1 or world > 1:
         from nfai_amd.pipeline import run_bench_pipeline
+        if not args.full:
+            args.pp_configs = "none"   # BASELINE config 5 over the same stages follows the headline with --full only
         run_bench_pipeline(args)
     else:
         out, weights = run_single(args)
         del weights
         want = args.configs == "auto" and not args.child and args.model == "llama-3.2-3b" and args.quant == "f16" and not args.stage_blocks
-        if want or args.configs == "all":
+        if args.full and (want or args.configs == "all"):
             import gc
             import torch
             gc.collect()

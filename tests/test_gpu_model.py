@@ -662,20 +662,35 @@ def test_full_size_parity_through_bench(quant, tmp_path):
     runs the oracle on the same weights (its `cpu_baseline` leg, here 6 tokens) and compares EVERY position's full logit vector
     with the GPU's, and compares the 512-token MFMA prefill with the token-by-token decode path.  The tolerances are the
     end-to-end ones of this file; the line must also carry the contract's roofline fields.  Also as Q4_K_M (BASELINE config 4:
-    Q4_K / Q6_K blocks; the oracle multiplies the dequantised weights).  The fp16 run is the driver's default command shape, so it
-    also appends `configs[]` — BASELINE configs 4, 2 (the whole 16-block Llama-3.2-1B) and config 5's per-GPU share (four 8B blocks
-    + the untied Q6_K lm_head), each in a child process with its own oracle comparison at full width and depth."""
+    Q4_K / Q6_K blocks; the oracle multiplies the dequantised weights).  The fp16 run is the default workload, so it also
+    appends `configs[]` — BASELINE configs 4, 2 (the whole 16-block Llama-3.2-1B) and config 5's per-GPU share (four 8B blocks
+    + the untied Q6_K lm_head), each in a child process with its own oracle comparison at full width and depth.  All of this is
+    `bench.py --full`; the plain run of the same arguments (the headline only) must time the same steps on the same inputs: the
+    same positions and KV capacity, and bit for bit the same last logits and token (the value path has no atomics)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+
+    def bench(dump, *extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "16", "--warmup", "2", "--cpu-tokens", "6", "--quant", quant,
+                            "--dump-outputs", dump, *extra], env=env, cwd=root, capture_output=True, text=True, timeout=1500)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        return json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+
     dump = str(tmp_path / "outputs")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "16", "--warmup", "2", "--cpu-tokens", "6", "--quant", quant,
-                        "--dump-outputs", dump], env=env, cwd=root, capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    d = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+    d = bench(dump, "--full")
+    plain_dump = str(tmp_path / "plain_outputs")
+    p = bench(plain_dump)
+    for k in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "dtype", "bytes_per_token"):
+        assert p[k] == d[k], k
+    assert p["value"] > 100 and abs(p["value"] - 1e3 / p["ms_per_step"]) < 1e-6 * p["value"]
+    assert {k: p["config"][k] for k in ("workload", "positions", "kv_capacity")} == {k: d["config"][k] for k in ("workload", "positions", "kv_capacity")}
+    assert not {"roofline", "prefill", "cpu_baseline", "short_context", "sampling_path", "configs"} & set(p), sorted(p)
+    for name in ("logits", "token"):
+        np.testing.assert_array_equal(np.load(os.path.join(plain_dump, name + ".npy")), np.load(os.path.join(dump, name + ".npy")))
     # --dump-outputs: what the last timed step returned, its greedy token being the argmax of its logits
     lg, tk = np.load(os.path.join(dump, "logits.npy")), np.load(os.path.join(dump, "token.npy"))
     assert lg.dtype == np.float32 and lg.shape == (synth.BY_NAME["llama-3.2-3b"].V,) and np.isfinite(lg).all()

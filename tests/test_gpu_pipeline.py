@@ -216,7 +216,8 @@ def test_pp_bad_arguments(env):
 def test_bench_two_rank_rehearsal_on_one_card():
     """`bench.py --gpus 2` started WITHOUT a launcher (the form the driver uses for N = 1) must start its own
     torch.distributed.run child; with NFAI_PP_REHEARSAL=1 both ranks share device 0 and exchange over gloo: HipStage + TorchComm
-    + the wavefront schedule in two real processes.  Checks the contract fields of the one JSON line rank 0 prints."""
+    + the wavefront schedule in two real processes.  Checks the contract fields of the one JSON line rank 0 prints (with --full, which
+    adds BASELINE config 5 over the same stages)."""
     import json
     import os
     import subprocess
@@ -226,7 +227,7 @@ def test_bench_two_rank_rehearsal_on_one_card():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--model", "llama-3.2-1b",
-                        "--context", "96"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
+                        "--context", "96", "--full"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)

@@ -1,7 +1,7 @@
 # 1B decode: tokens/s at long (512+) and short (16+) context for a few GEMV launch geometries (environment knobs of DESIGN 9)
-run() { env "$@" python bench.py --model llama-3.2-1b --steps 256 --warmup 8 --configs none --no-cpu-baseline --sample-tokens 0 --profile-steps 2 > gpurun_out/sw1b.json 2>/dev/null; python - "$*" <<'PY'
+run() { out=$(env "$@" python bench.py --full --model llama-3.2-1b --steps 256 --warmup 8 --configs none --no-cpu-baseline --sample-tokens 0 --profile-steps 2 2>/dev/null); python - "$*" "$out" <<'PY'
 import json,sys
-d=json.loads(open("gpurun_out/sw1b.json").read().strip().splitlines()[-1])
+d=json.loads(sys.argv[2].strip().splitlines()[-1])
 k={x["class"]:x["us_per_launch"] for x in d["roofline"]["kernels"]}
 print(f"{sys.argv[1]:60s} long {d['value']:7.1f}  short {d['short_context']['tokens_per_s']:7.1f}  {k}", flush=True)
 PY
