@@ -202,8 +202,8 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
     uint8_t *xa6 = MIXED ? smem + (size_t)kpad * 4 : xa;             // second fragment layout (Q6_K) when both are needed
     float *sums = reinterpret_cast<float *>(xa6 + (size_t)kpad * 4);  // [blk][G][4]: sums of x' per scale group
     float *sums6 = MIXED ? sums + nw * BPW * 16 : sums;
-    float *scl = sums6 + nw * BPW * 16;                               // [blk] 2^-S of the super-block's fixed-point scale
-    float *red = scl + nw * BPW;                                      // [2][UB][R][nw][64]
+    int *sexp = reinterpret_cast<int *>(sums6 + nw * BPW * 16);       // [blk] S of the super-block's fixed-point scale 2^S
+    float *red = reinterpret_cast<float *>(sexp + nw * BPW);          // [2][UB][R][nw][64]
     float *scal = red + 2 * UB * R * nw * 64;                       // 32 floats of reduction scratch
 
     const uint32_t nunits = (p.NU - blockIdx.x + gridDim.x - 1) / gridDim.x;
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
                 v[2] = v[2] * gv[i][2];
                 v[3] = v[3] * gv[i][3];
             }
-            kqm_stage<HAS4, HAS6, HAS8>(v, blk, lane, xa, xa6, sums, sums6, scl);
+            kqm_stage<HAS4, HAS6, HAS8>(v, blk, lane, xa, xa6, sums, sums6, sexp);
         }
         // no barrier: every LDS word written above is read only by this wave (LDS operations of a wave execute in order)
     }
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
 #pragma unroll
             for (int sl = 0; sl < 4; sl++) af[sl] = *reinterpret_cast<const i32x4 *>(abase + sl * 256);
         }
-        const float inv_scale = scl[blk];
+        const int sx = sexp[blk];
         if constexpr (HAS8) {
             a = q8t_dot(buf, af);
         } else {
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
                 }
             }
         }
-        acc += live ? a * inv_scale : 0.f;
+        acc += live ? ldexpf(a, -sx) : 0.f;  // back from x' = x * 2^S (S up to 170 or down to -106: no float 2^-S)
         ++cst;
         if (bi == BPW - 1) {
             const uint32_t slot = ui % UB;
@@ -688,6 +688,13 @@ hipError_t launch_embed_kqt(const void *table, int type, uint64_t n_rows, const 
 // lanes that expand them, an instruction wrote 64 separate 16-byte pieces in 64 different lines (13.2 us per tensor on average at
 // 3B, a third of the K-quant prefill).
 constexpr uint32_t DQ_ROW = 512 + 16;
+// fp16 of a product rounded as written: to fp32, then to fp16 (as the oracle's dequantisation).  Without the empty asm the backend
+// folds (_Float16)(a * b) into one v_fma_mix{lo,hi}_f16 a, b, 0: a single rounding, and +0 where a negative a times a zero b is -0.
+__device__ __forceinline__ _Float16 f16_of_f32(float v)
+{
+    asm("" : "+v"(v));
+    return (_Float16)v;
+}
 template <int QT>
 __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 *out, uint32_t n_tiles, uint32_t NB)
 {
@@ -739,7 +746,7 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
             for (int c = 0; c < 2; c++) {
                 f16x8 o;
 #pragma unroll
-                for (int e = 0; e < 8; e++) o[e] = (_Float16)(d * (float)(int8_t)((q[2 * c + (e >> 2)] >> (8 * (e & 3))) & 0xFFu));
+                for (int e = 0; e < 8; e++) o[e] = f16_of_f32(d * (float)(int8_t)((q[2 * c + (e >> 2)] >> (8 * (e & 3))) & 0xFFu));
                 *reinterpret_cast<f16x8 *>(orow + 64 * h + 16 * g + 8 * c) = o;
             }
         }
@@ -763,7 +770,7 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
                     const uint32_t j = c * 8 + e;
                     const uint32_t lb = (ql[j >> 2] >> (8 * (j & 3))) & 0xFFu, hb = (qh[j >> 2] >> (8 * (j & 3))) & 0xFFu;
                     const int q = (int)(((qd >= 2) ? (lb >> 4) : (lb & 0xFu)) | (((hb >> (2 * qd)) & 3u) << 4)) - 32;
-                    o[e] = (_Float16)(dsc * (float)q);
+                    o[e] = f16_of_f32(dsc * (float)q);
                 }
                 *reinterpret_cast<f16x8 *>(orow + n * 128 + qd * 32 + lh * 16 + c * 8) = o;
             }

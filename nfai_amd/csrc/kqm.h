@@ -203,23 +203,24 @@ __device__ __forceinline__ float q5t_dot(const Q5T &w, const i32x4 (&af)[4], f32
 // Fixed-point staging of ONE 256-element super-block of the activation vector by one wave (lane holds elements 4*lane .. +3, after the
 // optional RMSNorm): power-of-two scale so that |x * 2^S| < 2^22, three signed base-256 digits per element written as MFMA A
 // fragments [blk][slot:4][G][digit][16 B] (Q4_K / Q5_K layout in xa, Q6_K layout in xa6, Q8_0 layout in xa), the sums of x' per scale group
-// (K-quants only) and 2^-S.  Nothing written here is read by another wave.
+// (K-quants only) and the exponent S (sexp[blk]; the consumer applies ldexpf(partial, -S)).  Nothing written here is read by another wave.
+// S = 21 - ilogb(max|x|) for every finite non-zero maximum, fp32 subnormals (S up to 170) to FLT_MAX (S = -106) alike, and x is scaled
+// with ldexpf on the value, so neither 2^S nor 2^-S is ever formed as a float: every finite super-block keeps 22+ bits of its maximum.
+// An all-zero super-block stages zeros (S = 0).  Non-finite x is not supported: Inf / NaN in a super-block make its digits and sums
+// meaningless (the float -> int conversion of a non-finite value), and the launch's outputs with them.
 template <bool HAS4, bool HAS6, bool HAS8 = false>
 __device__ __forceinline__ void kqm_stage(const f32x4 v, const uint32_t blk, const uint32_t lane, uint8_t *xa, uint8_t *xa6, float *sums,
-                                          float *sums6, float *scl)
+                                          float *sums6, int *sexp)
 {
     const uint32_t k = lane * 4;  // position inside the super-block
     const float am = wave_max(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-    int S = 0;
-    if (am > 0.f && am < 3.0e38f) S = 21 - ilogbf(am);  // |x * 2^S| < 2^22: a 24-bit signed integer after rounding
-    S = max(-100, min(100, S));
-    const float scale = ldexpf(1.0f, S);
-    if (lane == 0) scl[blk] = ldexpf(1.0f, -S);
+    const int S = am > 0.f ? 21 - ilogbf(am) : 0;  // |x * 2^S| < 2^22: a 24-bit signed integer after rounding
+    if (lane == 0) sexp[blk] = S;
     uint32_t d0 = 0, d1 = 0, d2 = 0;  // digit planes of the four elements, one byte each
     float sx = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-        const float vs = v[e] * scale;
+        const float vs = ldexpf(v[e], S);
         const int xi = (int)rintf(vs);
         const int b0 = (int)(int8_t)(xi & 0xFF);
         const int r1 = (xi - b0) >> 8;

@@ -43,6 +43,15 @@ def tol(Wd, x):
     return 2e-6 * np.sqrt(Wd.shape[1] / 256.0) * s + 1e-6
 
 
+def stage_tol(Wd, x):
+    """Bound for the int8-MFMA GEMV with no absolute floor: x rounded to 24 bits relative to each 256-element super-block's largest
+    |x| (2^-21 * max|x_b| * sum_{k in b} |w_k|, twice the rounding error) plus the fp32 accumulation term of tol()."""
+    W, xa = np.abs(Wd.astype(np.float64)), np.abs(x.astype(np.float64))
+    N, K = W.shape
+    bmax = xa.reshape(K // 256, 256).max(axis=1)
+    return 2.0 ** -21 * (W.reshape(N, K // 256, 256).sum(axis=2) @ bmax) + 2e-6 * np.sqrt(K / 256.0) * (W @ xa)
+
+
 @pytest.mark.parametrize("qt", [Q4_K, Q6_K])
 @pytest.mark.parametrize("N,K", [(2048, 2048), (1024, 3072), (512, 8192), (96, 256), (40, 768), (300, 14336), (7, 4096), (64, 28672), (304, 14336)])
 def test_gemv_kquant(mgr, qt, N, K):
@@ -311,4 +320,9 @@ def test_gemv_kquant_activation_range(mgr, qt, xscale):
     got = op.GetOutputs()
     ref = orc.gemv(Wd, x)
     assert np.isfinite(got).all()
-    assert (np.abs(got - ref) <= tol(Wd, x) + 1e-30).all(), (np.abs(got - ref).max(), tol(Wd, x).min())
+    if xscale == 0.0:
+        assert (got == 0).all()
+    # no absolute floor: at 1e-30 every output is ~1e-29, and at 1e-6 the quiet super-blocks must keep their own 24 bits
+    bound = np.minimum(stage_tol(Wd, x), tol(Wd, x))
+    err = np.abs(got - ref)
+    assert (err <= bound).all(), (float((err / np.maximum(bound, 1e-300)).max()), float(err.max()), float(bound.min()))

@@ -52,6 +52,15 @@ def tol(Wd, x):
     return 2e-6 * np.sqrt(Wd.shape[1] / 256.0) * s + 1e-6
 
 
+def stage_tol(Wd, x):
+    """Bound for the int8-MFMA GEMV with no absolute floor: x rounded to 24 bits relative to each 256-element super-block's largest
+    |x| (2^-21 * max|x_b| * sum_{k in b} |w_k|, twice the rounding error) plus the fp32 accumulation term of tol()."""
+    W, xa = np.abs(Wd.astype(np.float64)), np.abs(x.astype(np.float64))
+    N, K = W.shape
+    bmax = xa.reshape(K // 256, 256).max(axis=1)
+    return 2.0 ** -21 * (W.reshape(N, K // 256, 256).sum(axis=2) @ bmax) + 2e-6 * np.sqrt(K / 256.0) * (W @ xa)
+
+
 def rng(seed):
     return np.random.Generator(np.random.PCG64(seed))
 
@@ -92,7 +101,13 @@ def test_gemv_q5_k_activation_range(mgr, xscale):
         x[256:512] *= 1e6  # one loud super-block beside quiet ones
     got = gemv(mgr, raw, N, K, x)
     assert np.isfinite(got).all()
-    assert (np.abs(got - orc.gemv(Wd, x)) <= tol(Wd, x) + 1e-30).all()
+    ref = orc.gemv(Wd, x)
+    if xscale == 0.0:
+        assert (got == 0).all()
+    # no absolute floor: at 1e-30 every output is ~1e-29, and at 1e-6 the quiet super-blocks must keep their own 24 bits
+    bound = np.minimum(stage_tol(Wd, x), tol(Wd, x))
+    err = np.abs(got - ref)
+    assert (err <= bound).all(), (float((err / np.maximum(bound, 1e-300)).max()), float(err.max()), float(bound.min()))
 
 
 @pytest.mark.parametrize("case", ["all_zero", "all_31", "every_qh_bit", "max_scales_mins", "one_qh_bit_per_row"])
