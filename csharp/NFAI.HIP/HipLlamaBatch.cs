@@ -1,0 +1,68 @@
+// Several sequences decoded in one step from a C# host: n models over ONE set of weights (a donor and models made with
+// nfai_hip_llama_share_tensors) advance one token each while every weight row is streamed from HBM once (nfai_hip_llama_batch_*).
+// The reference serves one sequence per LlamaModel (the token loop LlamaModel.cs:116-125); n conversations are n RunAsync loops of one
+// provider, each streaming all the weights again.  NOT compiled in this repository.
+namespace NFAI.HIP;
+
+public sealed unsafe class HipLlamaBatch : IDisposable
+{
+    private ulong handle;
+    public uint Count { get; }
+    public uint Vocab { get; }
+
+    /// <summary>models: 1 to 8 distinct, finalized, whole fp16 models of one HipBufferManager that read the same tensors
+    /// (HipLlamaModel.Handle).  The batch owns a workspace and its graphs, no weights and no KV cache: creating one is cheap, and a
+    /// host whose sequence has ended disposes the batch and makes a smaller one.  Throws with the member and the reason for
+    /// K-quant weights, pipeline stages, mixed KV types, separate weights, duplicates.</summary>
+    public HipLlamaBatch(ReadOnlySpan<ulong> models, uint vocab)
+    {
+        Count = (uint)models.Length; Vocab = vocab;
+        fixed (ulong* p = models) Native.Check(Native.nfai_hip_llama_batch_create(p, Count, out handle));
+    }
+
+    /// <summary>One token per member (one pass of LlamaModel.cs:116-125 for every sequence): tokens[i] runs at member i's own position
+    /// in member i's own cache; argmax[i] is the first index of member i's largest logit (SamplingUtils.cs:55-56).  logits: Count * Vocab
+    /// floats for hosts that sample themselves, or empty.  One graph launch and one synchronisation for all members.</summary>
+    public void Step(ReadOnlySpan<uint> tokens, Span<float> logits, Span<uint> argmax)
+    {
+        if (tokens.Length != Count || argmax.Length != Count) throw new ArgumentException("one token and one argmax slot per member");
+        if (!logits.IsEmpty && logits.Length != Count * Vocab) throw new ArgumentException("logits is [Count][Vocab] or empty", nameof(logits));
+        fixed (uint* t = tokens) fixed (float* l = logits) fixed (uint* a = argmax)
+            Native.Check(Native.nfai_hip_llama_batch_step(handle, t, logits.IsEmpty ? null : l, a));
+    }
+
+    /// <summary>nSteps tokens per member with every member's ArgMax fed back on the device (SamplingUtils.cs:43-57 in place of TopP):
+    /// tokensOut[s * Count + i] is member i's token after step s.</summary>
+    public void Greedy(ReadOnlySpan<uint> firstTokens, uint nSteps, Span<uint> tokensOut)
+    {
+        if (firstTokens.Length != Count || tokensOut.Length != nSteps * Count) throw new ArgumentException("tokensOut is [nSteps][Count]");
+        fixed (uint* f = firstTokens) fixed (uint* o = tokensOut)
+            Native.Check(Native.nfai_hip_llama_batch_greedy(handle, f, nSteps, o));
+    }
+
+    /// <summary>Algorithmic HBM bytes of one batch step at the members' current positions: every weight once + per member its KV rows.</summary>
+    public ulong BytesPerToken()
+    {
+        ulong total;
+        Native.Check(Native.nfai_hip_llama_batch_bytes_per_token(handle, &total));
+        return total;
+    }
+
+    /// <summary>One batch step launch by launch between events: (milliseconds, launches) per kernel class
+    /// (0 qkv, 1 attn, 2 wo, 3 gateup, 4 down, 5 lmhead, 6 other).  Every member advances by one token.</summary>
+    public (float[] Ms, uint[] Launches) ProfileStep(ReadOnlySpan<uint> tokens)
+    {
+        if (tokens.Length != Count) throw new ArgumentException("one token per member", nameof(tokens));
+        var ms = new float[8]; var n = new uint[8];
+        fixed (uint* t = tokens) fixed (float* m = ms) fixed (uint* c = n)
+            Native.Check(Native.nfai_hip_llama_batch_profile_step(handle, t, m, c));
+        return (ms, n);
+    }
+
+    public void Dispose()
+    {
+        if (handle == 0) return;
+        Native.Check(Native.nfai_hip_llama_batch_destroy(handle));
+        handle = 0;
+    }
+}

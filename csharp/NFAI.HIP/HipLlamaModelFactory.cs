@@ -45,6 +45,8 @@ public sealed class HipLlamaModelFactory : AbstractModelFactory
 public sealed unsafe class HipLlamaModel : IInferenceProvider
 {
     private readonly ulong model;
+    /// <summary>The native model handle (HipLlamaBatch takes the handles of the models it steps together).</summary>
+    public ulong Handle => model;
     private readonly Tokenizer tokenizer;
     private bool firstInput = true;
 

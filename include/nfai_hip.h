@@ -41,6 +41,7 @@ typedef uint64_t nfai_ctx_t;
 typedef uint64_t nfai_buf_t;
 typedef uint64_t nfai_model_t;
 typedef uint64_t nfai_pp_t;
+typedef uint64_t nfai_batch_t;
 
 enum nfai_status {
     NFAI_OK = 0,
@@ -344,6 +345,41 @@ int32_t nfai_hip_llama_profile_step(nfai_model_t model, uint32_t token, float *m
  * are replayed back to back, `reps` rounds, between a single pair of hipEvents on the launch stream (decode launches are
  * idempotent).  This is the per-launch duration rocprofv3 --kernel-trace reports; bench.py's roofline uses it. */
 int32_t nfai_hip_llama_profile_kernel(nfai_model_t model, uint32_t token, int32_t kernel_class, uint32_t reps, float *us_avg);
+
+/* ---- batched decode: n sequences advance one token each in ONE pass over the weights.  The reference serves one sequence per
+ *      LlamaModel (the token loop LlamaModel.cs:116-125); n conversations are n such loops, each streaming every weight again.  A
+ *      batch is a fixed, ordered set of 1..8 models that read the same tensors (a donor and models made with
+ *      nfai_hip_llama_share_tensors): every weight row is read once per step and applied to all members' activation vectors, and
+ *      member i's KV rows are read and written in member i's own cache at member i's own position.  fp16 matrices only. ---- */
+/* ≙ n LlamaModel instances over one set of weights entering the loop LlamaModel.cs:116-125 together.  The batch owns a workspace and
+ * its graphs, no weights and no KV cache; creation is cheap.  Members: distinct, finalized, whole models (layer_begin == 0,
+ * layer_end == n_layers) on one context, reading the same tensors, all matrices NFAI_F16 (norm gains F32), the fused path (neither
+ * NFAI_LLAMA_UNFUSED nor the engine), one KV element type.  NFAI_ERR_INVALID: dead handle, duplicate, n outside [1, 8], different
+ * contexts, not finalized.  NFAI_ERR_UNSUPPORTED: K-quant / Q8_0 weights, a pipeline stage, mixed KV types, separate weights, the 1:1
+ * or engine path.  nfai_hip_last_error names the member and the reason; nothing stays allocated.  A member stays a normal model:
+ * _decode_step, _ingest, _set_pos, _read, _read_kv, _pos work on it between batch steps and see the state the batch left. */
+int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_t n, nfai_batch_t *out);
+/* Frees the workspace and the graphs; the members are not touched (≙ leaving the loop LlamaModel.cs:116-125: the models live on). */
+int32_t nfai_hip_llama_batch_destroy(nfai_batch_t batch);
+/* ≙ one pass of the loop body LlamaModel.cs:116-125 for every member: tokens[i] is embedded, runs through every block at member
+ * i's position, lm_head, ArgMax (SamplingUtils.cs:55-56: the first index of the maximum); every member's position advances by one.
+ * Blocking: token words in from pinned memory, ONE hipGraphLaunch, ArgMax words and the error word back, one synchronisation.
+ * logits_host: [n][n_vocab] fp32 or NULL; argmax: [n] or NULL.  A member at its KV capacity: NFAI_ERR_KV_FULL before anything is
+ * enqueued, no member's position moves.  A member destroyed or re-finalized since _batch_create: NFAI_ERR_INVALID. */
+int32_t nfai_hip_llama_batch_step(nfai_batch_t batch, const uint32_t *tokens /* [n] */, float *logits_host /* [n][V] or NULL */,
+                                  uint32_t *argmax /* [n] */);
+/* ≙ n_steps passes of LlamaModel.cs:116-125 per member with ArgMax in place of TopP (SamplingUtils.cs:43-57) and the token fed back on
+ * the device, as nfai_hip_llama_decode_greedy: member i's ArgMax of step s is its token of step s + 1.  tokens_out[s * n + i]. */
+int32_t nfai_hip_llama_batch_greedy(nfai_batch_t batch, const uint32_t *first_tokens /* [n] */, uint32_t n_steps,
+                                    uint32_t *tokens_out /* [n_steps][n] */);
+/* Algorithmic HBM bytes of ONE batch step at the members' current positions: every weight once, plus per member its
+ * embedding row and its KV rows (p + 1 read, 1 written) — against n times nfai_hip_llama_bytes_per_token for n loops LlamaModel.cs:116-125. */
+int32_t nfai_hip_llama_batch_bytes_per_token(nfai_batch_t batch, uint64_t *total);
+/* One batch step (as _batch_step without results: every member advances) launch by launch between hipEvents: device time and launch
+ * count by kernel class, the ids of nfai_hip_llama_profile_step (slow path, for tools/batch_decode_bench.py; the reference has no
+ * counterpart: its loop LlamaModel.cs:116-125 is not instrumented). */
+int32_t nfai_hip_llama_batch_profile_step(nfai_batch_t batch, const uint32_t *tokens /* [n] */, float *ms_by_class /* 8 */,
+                                          uint32_t *launches_by_class /* 8 */);
 
 /* ---- layer pipeline across GPUs (no reference counterpart: the reference is single-device, it takes the last enumerated
  *      Vulkan device, VulkanHelper.cs:149-150).  One process per GPU owns a contiguous range of TransformerBlocks (a slice of

@@ -264,6 +264,58 @@ size_t attn_wo_extra_bytes(uint32_t H, uint32_t D);  // workspace behind attn_pa
 bool attn_wo_ok(const AttnArgs &a, const GemvArgs &g);
 hipError_t launch_attn_wo(const AttnArgs &a, const GemvArgs &g, hipStream_t s);
 
+// ---- batched decode (kernels_gemv_batch.hip): one weight stream applied to the activation vectors of up to 8 sequences ------------
+// Column b of a launch is sequence b: its own activation vectors, KV cache, position word.  Columns >= n are dead (a batch of 3 runs
+// the B = 4 kernel): they read column 0's input and store nothing.
+constexpr uint32_t BATCH_MAX = 8;
+struct BatchGemvArgs {
+    const void *W[3] = {nullptr, nullptr, nullptr};   // fp16 [seg_rows[i]][K]
+    uint32_t seg_rows[3] = {0, 0, 0};
+    uint32_t K = 0, n = 0;
+    int mode = 0;                      // GemvMode
+    const float *gamma = nullptr;      // non-null: RMSNorm prologue per column
+    float eps = 0.f;
+    const float *x[BATCH_MAX] = {};
+    float *y[BATCH_MAX] = {};
+    const float *res[BATCH_MAX] = {};
+    // GEMV_QKV_ROPE
+    void *kc[BATCH_MAX] = {}, *vc[BATCH_MAX] = {};
+    uint64_t kv_head_stride[BATCH_MAX] = {};
+    uint32_t cap[BATCH_MAX] = {};
+    const uint32_t *pos[BATCH_MAX] = {};
+    uint64_t kv_pos_stride = 0;
+    int kv_type = NFAI_F32;
+    const float *freqs = nullptr;
+    uint32_t rope_dims = 0, H = 0, Hkv = 0, D = 0;
+    uint32_t *err = nullptr;           // device word: 0x10000 | column when a column's position word is at or past its capacity
+    // GEMV_PLAIN (lm_head): first index of the maximum per column + the end-of-token bookkeeping of every member
+    void *am_work = nullptr;           // batch_argmax_bytes(), zeroed once
+    uint32_t *am_tok_batch = nullptr;  // [BATCH_MAX]: the batch's token words (next step's input)
+    uint32_t *am_tok[BATCH_MAX] = {}, *am_pos[BATCH_MAX] = {}, *am_ring[BATCH_MAX] = {};
+    uint32_t am_ring_len = 0;
+    uint32_t n_cu = 256;
+};
+constexpr size_t batch_argmax_bytes() { return (size_t)BATCH_MAX * 1024 * 8 + 256; }
+bool batch_gemv_ok(const BatchGemvArgs &a);   // shape rules of launch_batch_gemv (checked by nfai_hip_llama_batch_create)
+hipError_t launch_batch_gemv(const BatchGemvArgs &a, hipStream_t s);
+struct BatchAttnArgs {
+    uint32_t n = 0;
+    const float *q[BATCH_MAX] = {};
+    float *o[BATCH_MAX] = {};
+    const void *kc[BATCH_MAX] = {}, *vc[BATCH_MAX] = {};
+    uint64_t kv_head_stride[BATCH_MAX] = {};
+    uint32_t cap[BATCH_MAX] = {};
+    const uint32_t *pos[BATCH_MAX] = {};
+    uint64_t kv_pos_stride = 0;
+    int kv_type = NFAI_F32;
+    uint32_t H = 0, Hkv = 0, D = 0;
+    void *work = nullptr;              // batch_attn_bytes(), zeroed once
+};
+size_t batch_attn_bytes(uint32_t H, uint32_t D);
+hipError_t launch_batch_attn(const BatchAttnArgs &a, hipStream_t s);
+// x[b] = row tok[b] of the fp16 embedding table, widened (TokenEmbedShader.cs:131-159), b < n
+hipError_t launch_batch_embed(const void *table, uint64_t n_rows, uint32_t E, const uint32_t *tok, float *const *x, uint32_t n, hipStream_t s);
+
 // the weight-streaming engine (kernels_engine.hip): Wo + residual -> gate|up -> Wdown + residual -> next block's q|k|v, one launch
 struct EngineArgs {
     uint32_t n_ops = 3;              // 3: ends with Wdown (last block of the range); 4: + the next block's q|k|v

@@ -98,6 +98,8 @@ struct Model {
         std::shared_ptr<WideShadow> wide = std::make_shared<WideShadow>();
     } pf;
     uint32_t pos_host = 0;
+    uint64_t serial = 0;             // never reused: a batch (nfai_hip_llama_batch_create) tells a member from a later model at the same address
+    uint32_t weights_gen = 0;        // advanced whenever a tensor slot changes: a batch holds the pointers it was created over
     const float *x_last = nullptr;   // where the last enqueued token left the hidden state (m->x, or m->h on the engine path)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
@@ -711,6 +713,8 @@ NFAI_API int32_t nfai_hip_llama_create(nfai_ctx_t ch, const nfai_llama_desc *des
     NFAI_REQUIRE(d.rope_n_freqs <= d.rope_dims / 2, "llama_create: rope_n_freqs %u > rope_dims/2", d.rope_n_freqs);
     NFAI_REQUIRE(d.C <= 32768, "llama_create: KV capacity %u > 32768", d.C);
     Model *m = new Model();
+    static uint64_t next_serial = 0;
+    m->serial = ++next_serial;
     m->ctx = c;
     m->d = d;
     m->first_stage = d.layer_begin == 0;
@@ -916,6 +920,7 @@ static int set_tensor_impl(Model *m, const char *name, int type, uint64_t rows, 
     if (m->pf.wide.use_count() > 1) m->pf.wide = std::make_shared<WideShadow>();
     else std::fill(m->pf.wide->done.begin(), m->pf.wide->done.end(), 0);
     m->finalized = false;  // graphs captured over the old pointer are dropped by the next finalize
+    m->weights_gen++;
     if (t->owned && t->ptr) {
         hipStreamSynchronize(s);  // nothing enqueued may still read the old storage
         hipFree(t->ptr);
@@ -954,6 +959,7 @@ NFAI_API int32_t nfai_hip_llama_share_tensors(nfai_model_t h, nfai_model_t donor
     // widened by whichever model ran first, in stream order.  Another context's stream would race the re-widened single slot.
     m->pf.wide = src->ctx == m->ctx ? src->pf.wide : std::make_shared<WideShadow>();
     m->finalized = false;
+    m->weights_gen++;
     return NFAI_OK;
 }
 
@@ -1909,5 +1915,460 @@ NFAI_API int32_t nfai_hip_debug_read_kv_rows(nfai_model_t h, uint32_t layer, int
             memcpy(&hv, &tmp16[i], 2);
             host[i] = (float)hv;
         }
+    return NFAI_OK;
+}
+
+// ---- batched decode: n models ("slots" over one set of weights) advance one token each in ONE pass over the weights ---------------
+// What N concurrent token loops of the reference do N times over (LlamaModel.cs:116-125 per sequence), with every weight row read
+// once per step (kernels_gemv_batch.hip).  A batch owns a workspace and two graphs, no weights and no KV cache: column i of every
+// launch reads and writes member i's own activation vectors, cache, token word, ring and position word, so after a batch step each
+// member is in the state its own nfai_hip_llama_decode_step would have left.  Launches per token: 1 (embedding rows) + 5 per block
+// (q|k|v, attention, Wo, gate|up, Wdown) + 1 (lm_head + ArgMax + bookkeeping), a linear chain on the context's stream.
+namespace {
+
+struct Batch {
+    uint32_t magic = 0x4E464254;  // 'NFBT'
+    Ctx *ctx = nullptr;
+    uint32_t n = 0;
+    nfai_model_t handles[BATCH_MAX] = {};
+    Model *mem[BATCH_MAX] = {};
+    uint64_t serial[BATCH_MAX] = {};
+    uint32_t gen[BATCH_MAX] = {};
+    uint32_t *d_tok = nullptr;     // [0..7] token words (in: the step's tokens, out: the ArgMax), [8] error word
+    void *d_am = nullptr, *d_attn = nullptr;
+    uint32_t *h_pin = nullptr;     // [0..7] tokens in | [16..24] token words + error word out
+    hipGraph_t g_step = nullptr, g_body = nullptr;
+    hipGraphExec_t x_step = nullptr, x_body = nullptr;
+};
+
+Batch *batch_of(nfai_batch_t h)
+{
+    if (!handle_live(h)) return nullptr;
+    Batch *b = reinterpret_cast<Batch *>(h);
+    return b->magic == 0x4E464254 ? b : nullptr;
+}
+
+#define BATCH_OR_FAIL(bt, h)                                                      \
+    Batch *bt = batch_of(h);                                                      \
+    if (!bt) return fail(NFAI_ERR_INVALID, "%s: invalid batch handle", __func__); \
+    HIP_TRY(hipSetDevice(bt->ctx->device))
+
+// every member is still the model the batch was created over (a destroyed member is an error, not a crash)
+int batch_members_live(Batch *bt, const char *fn)
+{
+    for (uint32_t i = 0; i < bt->n; i++) {
+        Model *m = model_of(bt->handles[i]);
+        if (!m || m != bt->mem[i] || m->serial != bt->serial[i])
+            return fail(NFAI_ERR_INVALID, "%s: invalid member %u: the model was destroyed while the batch held it", fn, i);
+        if (!m->finalized || m->weights_gen != bt->gen[i])
+            return fail(NFAI_ERR_INVALID, "%s: invalid member %u: its tensors changed after the batch was created (make a new batch)", fn, i);
+    }
+    return NFAI_OK;
+}
+
+// The five launch forms of a block + the head, for the members of `bt` (also used, with nothing launched, to check the shapes).
+struct BatchOps {
+    Batch *bt;
+    BatchGemvArgs base() const
+    {
+        BatchGemvArgs a;
+        Model *m0 = bt->mem[0];
+        a.n = bt->n; a.eps = m0->d.eps; a.n_cu = (uint32_t)bt->ctx->prop.multiProcessorCount;
+        return a;
+    }
+    BatchGemvArgs qkv(size_t l) const
+    {
+        BatchGemvArgs a = base();
+        Model *m0 = bt->mem[0];
+        const nfai_llama_desc &d = m0->d;
+        const Layer &L = m0->layers[l];
+        a.W[0] = L.wq.ptr; a.W[1] = L.wk.ptr; a.W[2] = L.wv.ptr;
+        a.seg_rows[0] = (uint32_t)L.wq.rows; a.seg_rows[1] = (uint32_t)L.wk.rows; a.seg_rows[2] = (uint32_t)L.wv.rows;
+        a.K = d.E; a.mode = GEMV_QKV_ROPE; a.gamma = static_cast<const float *>(L.attn_norm.ptr);
+        for (uint32_t i = 0; i < bt->n; i++) {
+            Model *m = bt->mem[i];
+            a.x[i] = m->x; a.y[i] = m->q;
+            a.kc[i] = m->layers[l].kcache; a.vc[i] = m->layers[l].vcache;
+            a.kv_head_stride[i] = m->kv_head_stride; a.cap[i] = m->d.C; a.pos[i] = m->d_pos;
+        }
+        a.kv_pos_stride = m0->kv_pos_stride; a.kv_type = m0->kv_f16 ? NFAI_F16 : NFAI_F32;
+        a.freqs = m0->d_freqs; a.rope_dims = d.rope_dims; a.H = d.H; a.Hkv = d.Hkv; a.D = d.D;
+        a.err = bt->d_tok + BATCH_MAX;
+        return a;
+    }
+    BatchAttnArgs attn(size_t l) const
+    {
+        BatchAttnArgs a;
+        Model *m0 = bt->mem[0];
+        a.n = bt->n;
+        for (uint32_t i = 0; i < bt->n; i++) {
+            Model *m = bt->mem[i];
+            a.q[i] = m->q; a.o[i] = m->att; a.kc[i] = m->layers[l].kcache; a.vc[i] = m->layers[l].vcache;
+            a.kv_head_stride[i] = m->kv_head_stride; a.cap[i] = m->d.C; a.pos[i] = m->d_pos;
+        }
+        a.kv_pos_stride = m0->kv_pos_stride; a.kv_type = m0->kv_f16 ? NFAI_F16 : NFAI_F32;
+        a.H = m0->d.H; a.Hkv = m0->d.Hkv; a.D = m0->d.D; a.work = bt->d_attn;
+        return a;
+    }
+    BatchGemvArgs wo(size_t l) const
+    {
+        BatchGemvArgs a = base();
+        Model *m0 = bt->mem[0];
+        const Layer &L = m0->layers[l];
+        a.W[0] = L.wo.ptr; a.seg_rows[0] = (uint32_t)L.wo.rows; a.K = m0->d.H * m0->d.D; a.mode = GEMV_RESIDUAL;
+        for (uint32_t i = 0; i < bt->n; i++) { Model *m = bt->mem[i]; a.x[i] = m->att; a.res[i] = m->x; a.y[i] = m->h; }
+        return a;
+    }
+    BatchGemvArgs gateup(size_t l) const
+    {
+        BatchGemvArgs a = base();
+        Model *m0 = bt->mem[0];
+        const Layer &L = m0->layers[l];
+        a.W[0] = L.wgate.ptr; a.W[1] = L.wup.ptr; a.seg_rows[0] = (uint32_t)L.wgate.rows; a.seg_rows[1] = (uint32_t)L.wup.rows;
+        a.K = m0->d.E; a.mode = GEMV_GATEUP; a.gamma = static_cast<const float *>(L.ffn_norm.ptr);
+        for (uint32_t i = 0; i < bt->n; i++) { Model *m = bt->mem[i]; a.x[i] = m->h; a.y[i] = m->act; }
+        return a;
+    }
+    BatchGemvArgs down(size_t l) const
+    {
+        BatchGemvArgs a = base();
+        Model *m0 = bt->mem[0];
+        const Layer &L = m0->layers[l];
+        a.W[0] = L.wdown.ptr; a.seg_rows[0] = (uint32_t)L.wdown.rows; a.K = m0->d.F; a.mode = GEMV_RESIDUAL;
+        for (uint32_t i = 0; i < bt->n; i++) { Model *m = bt->mem[i]; a.x[i] = m->act; a.res[i] = m->h; a.y[i] = m->x; }
+        return a;
+    }
+    BatchGemvArgs head() const
+    {
+        BatchGemvArgs a = base();
+        Model *m0 = bt->mem[0];
+        const Tensor &hd = m0->output.ptr ? m0->output : m0->token_embd;  // tied when output.weight is absent (LlamaModel.cs:64-67)
+        a.W[0] = hd.ptr; a.seg_rows[0] = (uint32_t)hd.rows; a.K = m0->d.E; a.mode = GEMV_PLAIN;
+        a.gamma = static_cast<const float *>(m0->output_norm.ptr);
+        for (uint32_t i = 0; i < bt->n; i++) {
+            Model *m = bt->mem[i];
+            a.x[i] = m->x; a.y[i] = m->logits;
+            a.am_tok[i] = m->d_tok; a.am_pos[i] = m->d_pos; a.am_ring[i] = m->d_ring;
+        }
+        a.am_work = bt->d_am; a.am_tok_batch = bt->d_tok; a.am_ring_len = RING_LEN;
+        return a;
+    }
+};
+
+// One token of every member, enqueued on the stream.  ms / cnt (profiling, both or neither): hipEvents around every launch, by class.
+int enqueue_batch(Batch *bt, float *ms = nullptr, uint32_t *cnt = nullptr)
+{
+    hipStream_t s = bt->ctx->stream;
+    Model *m0 = bt->mem[0];
+    BatchOps ops{bt};
+    std::vector<hipEvent_t> ev;
+    std::vector<int> cls;
+    auto run = [&](int c, const std::function<hipError_t()> &f) -> int {
+        if (ms) {
+            hipEvent_t a, b;
+            HIP_TRY(hipEventCreate(&a));
+            HIP_TRY(hipEventCreate(&b));
+            ev.push_back(a); ev.push_back(b); cls.push_back(c);
+            HIP_TRY(hipEventRecord(a, s));
+        }
+        const hipError_t e = f();
+        if (e != hipSuccess)
+            return fail(e == hipErrorInvalidValue ? NFAI_ERR_INVALID : NFAI_ERR_HIP, "batch launch (class %d) failed: %s", c, hipGetErrorString(e));
+        if (ms) HIP_TRY(hipEventRecord(ev.back(), s));
+        return NFAI_OK;
+    };
+#define B_TRY(c, expr) S_TRY(run(c, [&]() -> hipError_t { return (expr); }))
+    float *xs[BATCH_MAX] = {};
+    for (uint32_t i = 0; i < bt->n; i++) xs[i] = bt->mem[i]->x;
+    B_TRY(KC_OTHER, launch_batch_embed(m0->token_embd.ptr, m0->token_embd.rows, m0->d.E, bt->d_tok, xs, bt->n, s));
+    for (size_t l = 0; l < m0->layers.size(); l++) {
+        B_TRY(KC_QKV, launch_batch_gemv(ops.qkv(l), s));
+        B_TRY(KC_ATTN, launch_batch_attn(ops.attn(l), s));
+        B_TRY(KC_WO, launch_batch_gemv(ops.wo(l), s));
+        B_TRY(KC_GATEUP, launch_batch_gemv(ops.gateup(l), s));
+        B_TRY(KC_DOWN, launch_batch_gemv(ops.down(l), s));
+    }
+    B_TRY(KC_LMHEAD, launch_batch_gemv(ops.head(), s));
+#undef B_TRY
+    if (ms) {
+        HIP_TRY(hipStreamSynchronize(s));
+        for (size_t i = 0; i < cls.size(); i++) {
+            float t = 0.f;
+            HIP_TRY(hipEventElapsedTime(&t, ev[2 * i], ev[2 * i + 1]));
+            ms[cls[i]] += t;
+            cnt[cls[i]]++;
+        }
+        for (hipEvent_t e : ev) hipEventDestroy(e);
+    }
+    return NFAI_OK;
+}
+
+// with_io: [token words H2D from pinned memory] -> the token -> [token words + error word D2H]; otherwise the token alone (greedy).
+int batch_capture(Batch *bt, bool with_io, hipGraph_t &g, hipGraphExec_t &x)
+{
+    if (x) return NFAI_OK;
+    hipStream_t s = bt->ctx->stream;
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = NFAI_OK;
+    hipError_t e = hipSuccess;
+    if (with_io) e = hipMemcpyAsync(bt->d_tok, bt->h_pin, bt->n * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) rc = enqueue_batch(bt);
+    if (e == hipSuccess && !rc && with_io) e = hipMemcpyAsync(bt->h_pin + 16, bt->d_tok, (BATCH_MAX + 1) * 4, hipMemcpyDeviceToHost, s);
+    hipGraph_t cg = nullptr;
+    const hipError_t e2 = hipStreamEndCapture(s, &cg);   // a stream left in capture mode would poison every later call
+    if (rc || e != hipSuccess || e2 != hipSuccess) {
+        if (cg) hipGraphDestroy(cg);
+        if (rc) return rc;
+        return fail(NFAI_ERR_HIP, "capturing the batch graph failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    }
+    g = cg;
+    HIP_TRY(hipGraphInstantiate(&x, g, nullptr, nullptr, 0));
+    return NFAI_OK;
+}
+
+void batch_free(Batch *bt)
+{
+    if (bt->x_step) hipGraphExecDestroy(bt->x_step);
+    if (bt->g_step) hipGraphDestroy(bt->g_step);
+    if (bt->x_body) hipGraphExecDestroy(bt->x_body);
+    if (bt->g_body) hipGraphDestroy(bt->g_body);
+    if (bt->d_tok) hipFree(bt->d_tok);
+    if (bt->d_am) hipFree(bt->d_am);
+    if (bt->d_attn) hipFree(bt->d_attn);
+    if (bt->h_pin) hipHostFree(bt->h_pin);
+    bt->magic = 0;
+    delete bt;
+}
+
+// A step failed on the device (the error word names the member): the token's results are not valid.  Every member's position
+// word goes back to the host's view, which did not move; the word is cleared for the next step.
+int batch_device_failed(Batch *bt, uint32_t code, const char *fn)
+{
+    hipStream_t s = bt->ctx->stream;
+    for (uint32_t i = 0; i < bt->n; i++) HIP_TRY(hipMemcpyAsync(bt->mem[i]->d_pos, &bt->mem[i]->pos_host, 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(bt->d_tok + BATCH_MAX, 0, 4, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    bt->h_pin[16 + BATCH_MAX] = 0;
+    const uint32_t i = code & 0xFFu;
+    return fail(NFAI_ERR_KV_FULL, "%s: member %u: its position word on the device was at or past its KV capacity %u (code 0x%x); no "
+                                  "member's position moved", fn, i, i < bt->n ? bt->mem[i]->d.C : 0u, code);
+}
+
+}  // namespace
+
+NFAI_API int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_t n, nfai_batch_t *out)
+{
+    if (!models || !out) return fail(NFAI_ERR_INVALID, "batch_create: null argument");
+    if (n < 1 || n > BATCH_MAX) return fail(NFAI_ERR_INVALID, "batch_create: invalid n = %u (a batch holds 1 to %u models)", n, BATCH_MAX);
+    Model *mem[BATCH_MAX] = {};
+    for (uint32_t i = 0; i < n; i++) {
+        mem[i] = model_of(models[i]);
+        if (!mem[i]) return fail(NFAI_ERR_INVALID, "batch_create: member %u: invalid model handle", i);
+        for (uint32_t j = 0; j < i; j++)
+            if (mem[j] == mem[i]) return fail(NFAI_ERR_INVALID, "batch_create: invalid member %u: the same model as member %u", i, j);
+    }
+    Model *m0 = mem[0];
+    for (uint32_t i = 0; i < n; i++)
+        if (mem[i]->ctx != m0->ctx) return fail(NFAI_ERR_INVALID, "batch_create: invalid member %u: it lives on another context than member 0", i);
+    HIP_TRY(hipSetDevice(m0->ctx->device));
+    for (uint32_t i = 0; i < n; i++) {
+        Model *m = mem[i];
+        if (!m->finalized) return fail(NFAI_ERR_INVALID, "batch_create: invalid member %u: call nfai_hip_llama_finalize first", i);
+        if (!(m->first_stage && m->last_stage))
+            return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member %u is a pipeline stage (blocks [%u, %u) of %u); a batch takes whole models", i,
+                        m->d.layer_begin, m->d.layer_end, m->d.L);
+        if (m->unfused || m->engine)
+            return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member %u runs the %s path; a batch takes models of the fused five-launch path", i,
+                        m->unfused ? "1:1 (NFAI_LLAMA_UNFUSED)" : "engine");
+        if (m->kv_f16 != m0->kv_f16)
+            return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member %u keeps an %s KV cache, member 0 an %s one; one element type per batch", i,
+                        m->kv_f16 ? "fp16" : "fp32", m0->kv_f16 ? "fp16" : "fp32");
+        auto f16 = [&](const Tensor &t, const char *what, size_t blk) -> int {
+            if (t.ptr && t.type != NFAI_F16)
+                return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member %u: %s of block %zu has ggml type %d; the batched kernels take fp16 matrices "
+                                                  "(K-quant and Q8_0 weights decode through nfai_hip_llama_decode_step)", i, what, blk, ggml_type_of(t.type));
+            return NFAI_OK;
+        };
+        S_TRY(f16(m->token_embd, "token_embd", 0));
+        S_TRY(f16(m->output, "output", 0));
+        for (size_t l = 0; l < m->layers.size(); l++) {
+            const Layer &L = m->layers[l];
+            S_TRY(f16(L.wq, "attn_q", l)); S_TRY(f16(L.wk, "attn_k", l)); S_TRY(f16(L.wv, "attn_v", l)); S_TRY(f16(L.wo, "attn_output", l));
+            S_TRY(f16(L.wgate, "ffn_gate", l)); S_TRY(f16(L.wup, "ffn_up", l)); S_TRY(f16(L.wdown, "ffn_down", l));
+        }
+        // the same tensors as member 0: a donor and models that called nfai_hip_llama_share_tensors on it, in any order
+        bool same = m->layers.size() == m0->layers.size() && m->token_embd.ptr == m0->token_embd.ptr && m->output.ptr == m0->output.ptr &&
+                    m->output_norm.ptr == m0->output_norm.ptr && m->d.E == m0->d.E && m->d.H == m0->d.H && m->d.Hkv == m0->d.Hkv &&
+                    m->d.D == m0->d.D && m->d.F == m0->d.F && m->d.V == m0->d.V && m->d.eps == m0->d.eps && m->d.rope_dims == m0->d.rope_dims &&
+                    m->d.rope_base == m0->d.rope_base && m->d.rope_n_freqs == m0->d.rope_n_freqs;
+        for (size_t l = 0; same && l < m->layers.size(); l++) {
+            const Layer &A = m->layers[l], &B = m0->layers[l];
+            same = A.attn_norm.ptr == B.attn_norm.ptr && A.wq.ptr == B.wq.ptr && A.wk.ptr == B.wk.ptr && A.wv.ptr == B.wv.ptr && A.wo.ptr == B.wo.ptr &&
+                   A.ffn_norm.ptr == B.ffn_norm.ptr && A.wgate.ptr == B.wgate.ptr && A.wup.ptr == B.wup.ptr && A.wdown.ptr == B.wdown.ptr;
+        }
+        if (!same)
+            return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member %u does not read the same tensors as member 0 (one copy of the weights per batch: "
+                                              "nfai_hip_llama_share_tensors)", i);
+    }
+    if (!m0->token_embd.ptr) return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member 0 has no token embedding");
+    Batch *bt = new Batch();
+    bt->ctx = m0->ctx;
+    bt->n = n;
+    for (uint32_t i = 0; i < n; i++) { bt->handles[i] = models[i]; bt->mem[i] = mem[i]; bt->serial[i] = mem[i]->serial; bt->gen[i] = mem[i]->weights_gen; }
+    // shapes the batched kernels take (nothing is allocated before this is known)
+    {
+        BatchOps ops{bt};
+        uint32_t dummy = 0;
+        bt->d_tok = &dummy; bt->d_am = &dummy; bt->d_attn = &dummy;   // placeholders for the argument checks only
+        const bool ok = batch_gemv_ok(ops.qkv(0)) && batch_gemv_ok(ops.wo(0)) && batch_gemv_ok(ops.gateup(0)) && batch_gemv_ok(ops.down(0)) &&
+                        batch_gemv_ok(ops.head()) && attn_group_ok(m0->d.H / m0->d.Hkv);
+        bt->d_tok = nullptr; bt->d_am = nullptr; bt->d_attn = nullptr;
+        if (!ok) {
+            const nfai_llama_desc &d = m0->d;
+            delete bt;
+            return fail(NFAI_ERR_UNSUPPORTED, "batch_create: the batched kernels do not take this shape at n = %u (E %u, F %u, H %u, Hkv %u, D %u, V %u)", n,
+                        d.E, d.F, d.H, d.Hkv, d.D, d.V);
+        }
+    }
+    auto bail = [&](int rc) { batch_free(bt); return rc; };
+    int rc;
+    if ((rc = dalloc(reinterpret_cast<void **>(&bt->d_tok), 256, bt->ctx->stream))) return bail(rc);
+    if ((rc = dalloc(&bt->d_am, batch_argmax_bytes(), bt->ctx->stream))) return bail(rc);
+    if ((rc = dalloc(&bt->d_attn, batch_attn_bytes(m0->d.H, m0->d.D), bt->ctx->stream))) return bail(rc);
+    if (hipHostMalloc(reinterpret_cast<void **>(&bt->h_pin), 256, hipHostMallocDefault) != hipSuccess) return bail(fail(NFAI_ERR_OOM, "batch_create: pinned staging"));
+    memset(bt->h_pin, 0, 256);
+    if (hipStreamSynchronize(bt->ctx->stream) != hipSuccess) return bail(fail(NFAI_ERR_HIP, "batch_create: stream synchronisation failed"));
+    handle_register(bt);
+    *out = reinterpret_cast<nfai_batch_t>(bt);
+    return NFAI_OK;
+}
+
+NFAI_API int32_t nfai_hip_llama_batch_destroy(nfai_batch_t h)
+{
+    BATCH_OR_FAIL(bt, h);
+    hipStreamSynchronize(bt->ctx->stream);
+    handle_unregister(bt);
+    batch_free(bt);
+    return NFAI_OK;
+}
+
+// the existing capacity error, for the first member that has no room for `steps` more tokens; nothing is enqueued
+static int batch_capacity(Batch *bt, uint32_t steps, const char *fn)
+{
+    for (uint32_t i = 0; i < bt->n; i++) {
+        Model *m = bt->mem[i];
+        if ((uint64_t)m->pos_host + steps > m->d.C)
+            return fail(NFAI_ERR_KV_FULL, "%s: member %u: KV cache full: %u step(s) from position %u exceed capacity %u (the reference would write out "
+                                          "of bounds here)", fn, i, steps, m->pos_host, m->d.C);
+    }
+    return NFAI_OK;
+}
+
+NFAI_API int32_t nfai_hip_llama_batch_step(nfai_batch_t h, const uint32_t *tokens, float *logits_host, uint32_t *argmax)
+{
+    BATCH_OR_FAIL(bt, h);
+    int rc;
+    if ((rc = batch_members_live(bt, "batch_step"))) return rc;
+    if (!tokens) return fail(NFAI_ERR_INVALID, "batch_step: null tokens");
+    const uint32_t V = bt->mem[0]->d.V;
+    for (uint32_t i = 0; i < bt->n; i++)
+        if (tokens[i] >= V) return fail(NFAI_ERR_INVALID, "batch_step: member %u: token %u >= vocab %u", i, tokens[i], V);
+    if ((rc = batch_capacity(bt, 1, "batch_step"))) return rc;
+    if ((rc = batch_capture(bt, true, bt->g_step, bt->x_step))) return rc;
+    hipStream_t s = bt->ctx->stream;
+    for (uint32_t i = 0; i < bt->n; i++) bt->h_pin[i] = tokens[i];
+    HIP_TRY(hipGraphLaunch(bt->x_step, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t code = bt->h_pin[16 + BATCH_MAX];
+    if (code) return batch_device_failed(bt, code, "batch_step");
+    for (uint32_t i = 0; i < bt->n; i++) {
+        bt->mem[i]->pos_host++;
+        bt->mem[i]->x_last = bt->mem[i]->x;
+        if (argmax) argmax[i] = bt->h_pin[16 + i];
+    }
+    if (logits_host) {
+        for (uint32_t i = 0; i < bt->n; i++)
+            HIP_TRY(hipMemcpyAsync(logits_host + (size_t)i * V, bt->mem[i]->logits, (size_t)V * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return NFAI_OK;
+}
+
+NFAI_API int32_t nfai_hip_llama_batch_greedy(nfai_batch_t h, const uint32_t *first_tokens, uint32_t n_steps, uint32_t *tokens_out)
+{
+    BATCH_OR_FAIL(bt, h);
+    int rc;
+    if ((rc = batch_members_live(bt, "batch_greedy"))) return rc;
+    if (!first_tokens || !tokens_out) return fail(NFAI_ERR_INVALID, "batch_greedy: null argument");
+    if (n_steps == 0 || n_steps > RING_LEN) return fail(NFAI_ERR_INVALID, "batch_greedy: n_steps = %u outside [1, %u]", n_steps, RING_LEN);
+    const uint32_t V = bt->mem[0]->d.V;
+    for (uint32_t i = 0; i < bt->n; i++)
+        if (first_tokens[i] >= V) return fail(NFAI_ERR_INVALID, "batch_greedy: member %u: token %u >= vocab %u", i, first_tokens[i], V);
+    if ((rc = batch_capacity(bt, n_steps, "batch_greedy"))) return rc;
+    if ((rc = batch_capture(bt, false, bt->g_body, bt->x_body))) return rc;
+    hipStream_t s = bt->ctx->stream;
+    for (uint32_t i = 0; i < bt->n; i++) bt->h_pin[i] = first_tokens[i];
+    HIP_TRY(hipMemcpyAsync(bt->d_tok, bt->h_pin, bt->n * 4, hipMemcpyHostToDevice, s));
+    // the feedback stays on the device: the lm_head launch leaves every member's ArgMax in the batch's token words
+    for (uint32_t st = 0; st < n_steps; st++) HIP_TRY(hipGraphLaunch(bt->x_body, s));
+    std::vector<uint32_t> ring((size_t)bt->n * RING_LEN);
+    for (uint32_t i = 0; i < bt->n; i++)
+        HIP_TRY(hipMemcpyAsync(ring.data() + (size_t)i * RING_LEN, bt->mem[i]->d_ring, RING_LEN * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(bt->h_pin + 16, bt->d_tok, (BATCH_MAX + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t code = bt->h_pin[16 + BATCH_MAX];
+    if (code) return batch_device_failed(bt, code, "batch_greedy");
+    for (uint32_t i = 0; i < bt->n; i++) {
+        Model *m = bt->mem[i];
+        for (uint32_t st = 0; st < n_steps; st++) tokens_out[(size_t)st * bt->n + i] = ring[(size_t)i * RING_LEN + (m->pos_host + st) % RING_LEN];
+        m->pos_host += n_steps;
+        m->x_last = m->x;
+    }
+    return NFAI_OK;
+}
+
+NFAI_API int32_t nfai_hip_llama_batch_bytes_per_token(nfai_batch_t h, uint64_t *total)
+{
+    BATCH_OR_FAIL(bt, h);
+    int rc;
+    if ((rc = batch_members_live(bt, "batch_bytes_per_token"))) return rc;
+    Model *m0 = bt->mem[0];
+    const nfai_llama_desc &d = m0->d;
+    uint64_t t = 0;
+    for (const Layer &L : m0->layers)   // every weight byte once per step (W + n KV(p))
+        t += tensor_bytes(L.wq) + tensor_bytes(L.wk) + tensor_bytes(L.wv) + tensor_bytes(L.wo) + tensor_bytes(L.wgate) + tensor_bytes(L.wup) + tensor_bytes(L.wdown);
+    t += tensor_bytes(m0->output.ptr ? m0->output : m0->token_embd);
+    for (uint32_t i = 0; i < bt->n; i++) {   // per member: its embedding row, its KV rows read (p + 1 positions) and written (1)
+        Model *m = bt->mem[i];
+        t += weight_row_bytes(m0->token_embd.type, d.E);
+        t += (uint64_t)m0->layers.size() * (2ull * d.Hkv * d.D * m->kv_esz * ((uint64_t)m->pos_host + 1) + 2ull * d.Hkv * d.D * m->kv_esz);
+    }
+    if (total) *total = t;
+    return NFAI_OK;
+}
+
+// One batch step launch by launch between hipEvents (slow path, for tools/batch_decode_bench.py): device time and launch count by
+// kernel class (the ids of nfai_hip_llama_profile_step).  It IS a step: every member advances by one token.
+NFAI_API int32_t nfai_hip_llama_batch_profile_step(nfai_batch_t h, const uint32_t *tokens, float *ms_by_class, uint32_t *launches_by_class)
+{
+    BATCH_OR_FAIL(bt, h);
+    int rc;
+    if ((rc = batch_members_live(bt, "batch_profile_step"))) return rc;
+    if (!tokens || !ms_by_class || !launches_by_class) return fail(NFAI_ERR_INVALID, "batch_profile_step: null argument");
+    const uint32_t V = bt->mem[0]->d.V;
+    for (uint32_t i = 0; i < bt->n; i++)
+        if (tokens[i] >= V) return fail(NFAI_ERR_INVALID, "batch_profile_step: member %u: token %u >= vocab %u", i, tokens[i], V);
+    if ((rc = batch_capacity(bt, 1, "batch_profile_step"))) return rc;
+    hipStream_t s = bt->ctx->stream;
+    for (uint32_t i = 0; i < bt->n; i++) bt->h_pin[i] = tokens[i];
+    HIP_TRY(hipMemcpyAsync(bt->d_tok, bt->h_pin, bt->n * 4, hipMemcpyHostToDevice, s));
+    for (int c = 0; c < KC_N; c++) { ms_by_class[c] = 0.f; launches_by_class[c] = 0; }
+    if ((rc = enqueue_batch(bt, ms_by_class, launches_by_class))) return rc;
+    HIP_TRY(hipMemcpyAsync(bt->h_pin + 16, bt->d_tok, (BATCH_MAX + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t code = bt->h_pin[16 + BATCH_MAX];
+    if (code) return batch_device_failed(bt, code, "batch_profile_step");
+    for (uint32_t i = 0; i < bt->n; i++) { bt->mem[i]->pos_host++; bt->mem[i]->x_last = bt->mem[i]->x; }
     return NFAI_OK;
 }

@@ -326,6 +326,65 @@ class LlamaModel:
             self.handle = None
 
 
+class LlamaBatch:
+    """n LlamaModel instances over ONE set of weights advancing together: what n concurrent token loops (LlamaModel.cs:116-125) do,
+    with every weight row read once per step (nfai_hip_llama_batch_*).  `models`: 1 to 8 whole fp16 models on one buffer manager,
+    one of them the donor of the others (`share_from`).  Each member keeps its own KV cache and position and stays a normal
+    LlamaModel: Step / Ingest / SetPos on a member between batch steps are seen by the next batch step."""
+
+    def __init__(self, models):
+        self.models = list(models)
+        self.n = len(self.models)
+        hs = (_lib.H * max(self.n, 1))(*[m.handle.value if isinstance(m.handle, _lib.H) else int(m.handle) for m in self.models])
+        h = _lib.H()
+        call("nfai_hip_llama_batch_create", hs, self.n, C.byref(h))
+        self.handle = h
+        self.V = int(self.models[0].dims["V"])
+
+    def Step(self, tokens, want_logits: bool = True):
+        """One token per member: (logits[n][V] | None, argmax[n])."""
+        t = np.ascontiguousarray(tokens, np.uint32)
+        if t.size != self.n:
+            raise ValueError(f"LlamaBatch.Step: {t.size} tokens for {self.n} members")
+        logits = np.empty((self.n, self.V), np.float32) if want_logits else None
+        am = np.empty(self.n, np.uint32)
+        call("nfai_hip_llama_batch_step", self.handle, t.ctypes.data_as(C.POINTER(C.c_uint32)),
+             logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None, am.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return logits, am
+
+    def Greedy(self, first_tokens, n_steps: int) -> np.ndarray:
+        """n_steps tokens per member with the ArgMax fed back on the device: tokens[n_steps][n]."""
+        t = np.ascontiguousarray(first_tokens, np.uint32)
+        if t.size != self.n:
+            raise ValueError(f"LlamaBatch.Greedy: {t.size} tokens for {self.n} members")
+        out = np.empty((int(n_steps), self.n), np.uint32)
+        call("nfai_hip_llama_batch_greedy", self.handle, t.ctypes.data_as(C.POINTER(C.c_uint32)), int(n_steps),
+             out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out
+
+    def BytesPerToken(self) -> int:
+        """Algorithmic HBM bytes of one batch step at the members' current positions."""
+        t = C.c_uint64()
+        call("nfai_hip_llama_batch_bytes_per_token", self.handle, C.byref(t))
+        return t.value
+
+    def ProfileStep(self, tokens):
+        """One batch step launch by launch: {class: (ms, launches)}; every member advances by one token."""
+        t = np.ascontiguousarray(tokens, np.uint32)
+        if t.size != self.n:
+            raise ValueError(f"LlamaBatch.ProfileStep: {t.size} tokens for {self.n} members")
+        ms = (C.c_float * 8)()
+        n = (C.c_uint32 * 8)()
+        call("nfai_hip_llama_batch_profile_step", self.handle, t.ctypes.data_as(C.POINTER(C.c_uint32)), ms, n)
+        names = ["qkv", "attn", "wo", "gateup", "down", "lmhead", "other", "engine"]
+        return {k: (ms[i], n[i]) for i, k in enumerate(names)}
+
+    def Dispose(self) -> None:
+        if self.handle is not None:
+            call("nfai_hip_llama_batch_destroy", self.handle)
+            self.handle = None
+
+
 class LlamaModelFactory:
     """≙ LlamaModelFactory (LlamaModelFactory.cs:7-45): the plugin hook AbstractModelFactory.TryCreate."""
 

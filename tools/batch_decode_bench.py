@@ -1,0 +1,239 @@
+"""Batched decode (nfai_hip_llama_batch_*) against the same sequences stepped one after another, in the same run.
+
+Llama-3.2-3B and -1B, fp16 weights built in HBM (bench.gen_weights_hbm), 8 models over one copy of the weights (fp32 KV caches, the
+library's default), each after a 512-token _ingest of its own prompt.  For n in {1, 2, 4, 8}, from position 517 of every member:
+
+  batch        n members through _batch_greedy (one graph replay per step for all of them)
+  sequential   the same n members through the existing _decode_enqueue path, one token each per round, round after round: how n
+               sequences are served without the batch (that path's code is unchanged)
+
+The two alternate window by window (>= 3 windows of --steps steps each, every window from the same positions, one untimed warm-up
+window of each first); reported: the median and the relative spread (max - min) / median of each, the ratio, the algorithmic bytes
+of one step (_batch_bytes_per_token) and of the n sequential steps, the fraction of the byte-model ratio reached, the step's
+fraction of 8 TB/s, and per kernel class the eager hipEvent time per launch of one batch step (_batch_profile_step) with its
+algorithmic bytes and fraction of the HBM roofline.  Parity: max |dlogit| of the batch against the members' own _decode_step at depth
+(4 positions, n = 4, same run), and against the CPU oracle for n = 4 on the 1B model at shallow staggered depths (--no-check skips
+the oracle, which takes about a minute of host time).  One JSON line; --out writes it to a file too.
+
+    python tools/batch_decode_bench.py --out profiles/batch_decode.json
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT]
+
+HBM_PEAK = 8.0e12
+T, WARM, NMAX = 512, 5, 8
+CLASSES = ["qkv", "attn", "wo", "gateup", "down", "lmhead", "other"]
+
+
+def class_bytes(weights, dims, positions, kv_esz=4):
+    """Algorithmic HBM bytes of ONE launch of each class of a batch step: the weights once, per member its KV rows."""
+    KD = dims.Hkv * dims.D
+    n = len(positions)
+    def wb(name):
+        t = weights[name][0]
+        return t.numel() * t.element_size()
+    def avg(*parts):
+        return sum(wb(f"blk.{i}.{p}.weight") for i in range(dims.L) for p in parts) / dims.L
+    head = "output.weight" if "output.weight" in weights else "token_embd.weight"
+    return {"qkv": avg("attn_q", "attn_k", "attn_v") + n * 2 * KD * kv_esz, "attn": sum(2 * KD * kv_esz * (p + 1) for p in positions),
+            "wo": avg("attn_output"), "gateup": avg("ffn_gate", "ffn_up"), "down": avg("ffn_down"), "lmhead": wb(head),
+            "other": n * dims.E * 2}
+
+
+def spread(xs):
+    return (max(xs) - min(xs)) / statistics.median(xs)
+
+
+def run_model(torch, dims, steps, windows):
+    import bench as B
+    from nfai_amd import synth
+    from nfai_amd.hip import HipBufferManager
+    from nfai_amd.llama_model import LlamaBatch, LlamaModel
+    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant="f16")
+    C = T + WARM + steps + 16
+    mgr = HipBufferManager(0)
+    dd = dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0)
+    md = synth.make_metadata(dims)
+    wt = {k: (t.data_ptr(), ty, r, c) for k, (t, ty, r, c) in weights.items()}
+    members = [LlamaModel(mgr, md, wt, C, max_batch=T, dims=dd)]
+    for _ in range(1, NMAX):
+        members.append(LlamaModel(mgr, md, wt, C, max_batch=T, dims=dd, share_from=members[0]))
+    first = []
+    for s, m in enumerate(members):   # every member its own prompt; the tokens of positions 512..516 through its own decode path
+        prompt = synth.make_tokens(dims, T, seed=99 + s)
+        prompt[0] = 128000 % dims.V
+        m.Ingest(prompt)
+        tok = int(prompt[-1])
+        for _ in range(WARM):
+            _, tok = m.Step(tok, want_logits=False)
+        first.append(tok)
+    p0 = T + WARM
+
+    def rewind(ms):
+        for m in ms:
+            m.SetPos(p0)
+
+    out = {"model": dims.name, "weights": "f16", "kv_cache": "f32", "positions": [p0, p0 + steps - 1], "steps_per_window": steps, "by_n": {}}
+    for n in (1, 2, 4, 8):
+        ms = members[:n]
+        batch = LlamaBatch(ms)
+
+        def batch_window():
+            rewind(ms)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            batch.Greedy(first[:n], steps)
+            return time.perf_counter() - t0
+
+        def seq_window():
+            rewind(ms)
+            for m, tok in zip(ms, first):
+                m.SetToken(tok)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                for m in ms:
+                    m.Enqueue(1)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+        batch_window()   # untimed: graph capture, code objects, every shape of the window
+        seq_window()
+        bt, sq = [], []
+        for _ in range(windows):   # alternating, same positions
+            bt.append(batch_window())
+            sq.append(seq_window())
+        b_tps = [n * steps / t for t in bt]
+        s_tps = [n * steps / t for t in sq]
+        rewind(ms)
+        for m in ms:   # the byte model at the middle of the window
+            m.SetPos(p0 + steps // 2)
+        bytes_batch = batch.BytesPerToken()
+        bytes_seq = sum(m.BytesPerToken(p0 + steps // 2)[0] for m in ms)
+        rewind(ms)
+        prof = batch.ProfileStep(first[:n])   # eager, one step (it advances the members)
+        prof = batch.ProfileStep(first[:n])
+        cb = class_bytes(weights, dims, [p0 + 1] * n)
+        classes = {}
+        for c in CLASSES:
+            ms_c, launches = prof[c]
+            if not launches:
+                continue
+            us = ms_c * 1e3 / launches
+            classes[c] = {"us_per_launch": us, "launches_per_step": launches, "bytes_per_launch": int(cb[c]),
+                          "frac_hbm_roofline": cb[c] / HBM_PEAK / (us * 1e-6) if us > 0 else None}
+        med_b, med_s = statistics.median(b_tps), statistics.median(s_tps)
+        ms_step = statistics.median(bt) / steps * 1e3
+        res = {"batch_ms_per_step": ms_step, "batch_tokens_per_s": med_b, "batch_windows_tokens_per_s": b_tps, "batch_spread": spread(b_tps),
+               "sequential_tokens_per_s": med_s, "sequential_windows_tokens_per_s": s_tps, "sequential_spread": spread(s_tps),
+               "speedup": med_b / med_s, "above_sequential_by_more_than_its_spread": med_b > med_s * (1 + spread(s_tps)),
+               "batch_bytes_per_step": bytes_batch, "sequential_bytes_per_round": bytes_seq, "byte_model_ratio": bytes_batch / bytes_seq,
+               "fraction_of_byte_model_reached": (med_b / med_s) / (bytes_seq / bytes_batch),
+               "step_frac_of_8TBps": bytes_batch / (ms_step * 1e-3) / HBM_PEAK, "launches_per_step": sum(v[1] for v in prof.values()),
+               "kernel_classes": classes}
+        if n == 4:   # the batch against the members' own decode path at depth, 4 positions
+            rewind(ms)
+            cur, worst, top = list(first[:n]), 0.0, 0.0
+            solo = []
+            for i, m in enumerate(ms):
+                tok, rows = first[i], []
+                for _ in range(4):
+                    lg, tok = m.Step(tok)
+                    rows.append(lg)
+                solo.append(rows)
+            rewind(ms)
+            for p in range(4):
+                lg, am = batch.Step(cur)
+                for i in range(n):
+                    worst = max(worst, float(np.abs(lg[i] - solo[i][p]).max()))
+                    top = max(top, float(np.abs(solo[i][p]).max()))
+                cur = [int(np.argmax(solo[i][p])) for i in range(n)]
+            res["parity_vs_decode_step_at_depth"] = {"positions": [p0, p0 + 3], "max_abs_logit_diff": worst, "max_abs_logit": top}
+        out["by_n"][str(n)] = res
+        batch.Dispose()
+    for m in reversed(members):
+        m.Dispose()
+    mgr.Dispose()
+    return out
+
+
+def oracle_parity(torch, dims, n=4):
+    """n = 4 on full-size weights at shallow staggered depths (the oracle walks every earlier token on the host): max |dlogit| over 4 steps."""
+    import bench as B
+    import oracle as orc
+    from nfai_amd import synth
+    from nfai_amd.hip import HipBufferManager
+    from nfai_amd.llama_model import LlamaBatch, LlamaModel
+    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant="f16")
+    C = 32
+    mgr = HipBufferManager(0)
+    dd = dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0)
+    md = synth.make_metadata(dims)
+    wt = {k: (t.data_ptr(), ty, r, c) for k, (t, ty, r, c) in weights.items()}
+    ms = [LlamaModel(mgr, md, wt, C, dims=dd)]
+    for _ in range(1, n):
+        ms.append(LlamaModel(mgr, md, wt, C, dims=dd, share_from=ms[0]))
+    host = {k: t.cpu().numpy() for k, (t, ty, r, c) in weights.items()}
+    toks = [synth.make_tokens(dims, 24, seed=400 + s) for s in range(n)]
+    refs = []
+    for s in range(n):
+        ref = orc.OracleLlama(orc.LlamaDesc(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, C=C), host)
+        for t in toks[s][:2 + 3 * s]:
+            ms[s].Step(int(t), want_logits=False)
+            ref.step(int(t), want_logits=False)
+        refs.append(ref)
+    batch = LlamaBatch(ms)
+    worst, top, same = 0.0, 0.0, []
+    for i in range(4):
+        st = [int(toks[s][2 + 3 * s + i]) for s in range(n)]
+        lg, am = batch.Step(st)
+        for s in range(n):
+            want = refs[s].step(st[s])
+            worst = max(worst, float(np.abs(lg[s] - want).max()))
+            top = max(top, float(np.abs(want).max()))
+            same.append(int(orc.argmax(want)) == int(am[s]))
+    batch.Dispose()
+    for m in reversed(ms):
+        m.Dispose()
+    mgr.Dispose()
+    return {"model": dims.name, "n": n, "positions_of_member_0": [2, 5], "max_abs_logit_diff": worst, "max_abs_logit": top, "argmax_equal": same}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--only", default="", metavar="MODEL", help="one model, e.g. llama-3.2-3b")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    from nfai_amd import synth
+    torch.cuda.set_device(0)
+    out = {"tool": "batch_decode_bench", "models": []}
+    for dims in (synth.LLAMA_32_3B, synth.LLAMA_32_1B):
+        if a.only and a.only != dims.name:
+            continue
+        out["models"].append(run_model(torch, dims, a.steps, max(3, a.windows)))
+        torch.cuda.empty_cache()
+    if not a.no_check:
+        out["parity_vs_oracle"] = oracle_parity(torch, synth.LLAMA_32_1B)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
