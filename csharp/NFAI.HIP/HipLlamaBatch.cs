@@ -13,12 +13,18 @@ public sealed unsafe class HipLlamaBatch : IDisposable
     /// <summary>models: 1 to 8 distinct, finalized, whole fp16 models of one HipBufferManager that read the same tensors
     /// (HipLlamaModel.Handle).  The batch owns a workspace and its graphs, no weights and no KV cache: creating one is cheap, and a
     /// host whose sequence has ended disposes the batch and makes a smaller one.  Throws with the member and the reason for
-    /// K-quant weights, pipeline stages, mixed KV types, separate weights, duplicates.</summary>
-    public HipLlamaBatch(ReadOnlySpan<ulong> models, uint vocab)
+    /// K-quant weights (unless quantized), pipeline stages, mixed KV types, separate weights, duplicates.</summary>
+    /// quantized: also admits members whose matrices are all Q4_K / Q6_K (Q4_K_M files) through nfai_hip_llama_batch_create_ex with
+    /// NFAI_BATCH_QUANT: every quantised row is read and unpacked once per step and multiplied on the matrix cores for all members.
+    public HipLlamaBatch(ReadOnlySpan<ulong> models, uint vocab, bool quantized = false)
     {
         Count = (uint)models.Length; Vocab = vocab;
-        fixed (ulong* p = models) Native.Check(Native.nfai_hip_llama_batch_create(p, Count, out handle));
+        fixed (ulong* p = models)
+            Native.Check(quantized ? Native.nfai_hip_llama_batch_create_ex(p, Count, BatchQuant, out handle)
+                                   : Native.nfai_hip_llama_batch_create(p, Count, out handle));
     }
+
+    private const uint BatchQuant = 1u;   // NFAI_BATCH_QUANT (nfai_hip.h)
 
     /// <summary>One token per member (one pass of LlamaModel.cs:116-125 for every sequence): tokens[i] runs at member i's own position
     /// in member i's own cache; argmax[i] is the first index of member i's largest logit (SamplingUtils.cs:55-56).  logits: Count * Vocab

@@ -350,7 +350,8 @@ int32_t nfai_hip_llama_profile_kernel(nfai_model_t model, uint32_t token, int32_
  *      LlamaModel (the token loop LlamaModel.cs:116-125); n conversations are n such loops, each streaming every weight again.  A
  *      batch is a fixed, ordered set of 1..8 models that read the same tensors (a donor and models made with
  *      nfai_hip_llama_share_tensors): every weight row is read once per step and applied to all members' activation vectors, and
- *      member i's KV rows are read and written in member i's own cache at member i's own position.  fp16 matrices only. ---- */
+ *      member i's KV rows are read and written in member i's own cache at member i's own position.  fp16 matrices, or Q4_K / Q6_K
+ *      ones through nfai_hip_llama_batch_create_ex. ---- */
 /* ≙ n LlamaModel instances over one set of weights entering the loop LlamaModel.cs:116-125 together.  The batch owns a workspace and
  * its graphs, no weights and no KV cache; creation is cheap.  Members: distinct, finalized, whole models (layer_begin == 0,
  * layer_end == n_layers) on one context, reading the same tensors, all matrices NFAI_F16 (norm gains F32), the fused path (neither
@@ -359,6 +360,20 @@ int32_t nfai_hip_llama_profile_kernel(nfai_model_t model, uint32_t token, int32_
  * or engine path.  nfai_hip_last_error names the member and the reason; nothing stays allocated.  A member stays a normal model:
  * _decode_step, _ingest, _set_pos, _read, _read_kv, _pos work on it between batch steps and see the state the batch left. */
 int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_t n, nfai_batch_t *out);
+/* ≙ the same n LlamaModel instances entering the loop LlamaModel.cs:116-125 together, on weights the reference cannot load at all
+ * (Parser.cs:111-114 rejects every quantised ggml type).  flags = 0: exactly nfai_hip_llama_batch_create.  NFAI_BATCH_QUANT also
+ * admits members whose matrices (token_embd and output included) are all Q4_K or Q6_K in any per-tensor mix, as _set_tensor +
+ * _finalize leave them for Q4_K_M files: one step reads every quantised row once, unpacks it once and multiplies it on the matrix
+ * cores with the fixed-point activations of all members (kernels_gemv_batch_kqm.hip); a q|k|v whose matrices differ in type runs as
+ * two launches.  NFAI_ERR_INVALID: unknown flag bits, and everything _batch_create answers so.  NFAI_ERR_UNSUPPORTED under the flag,
+ * naming member, tensor and ggml type: Q5_K / Q8_0 matrices, fp16 and quantised matrices in one model, a quantised matrix whose row
+ * count is not a multiple of 16 (the VALU fallback), a shape the kernels' LDS plan does not hold, and every refusal of _batch_create.
+ * The handle works with _batch_step, _batch_greedy, _batch_bytes_per_token (quantised bytes: every T16 plane and norm gain once, an
+ * embedding row per member where the table is not the head's, each member's KV rows), _batch_profile_step and _batch_destroy. */
+enum nfai_batch_flags {
+    NFAI_BATCH_QUANT = 1u << 0,   /* admit members whose matrices are all Q4_K / Q6_K */
+};
+int32_t nfai_hip_llama_batch_create_ex(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out);
 /* Frees the workspace and the graphs; the members are not touched (≙ leaving the loop LlamaModel.cs:116-125: the models live on). */
 int32_t nfai_hip_llama_batch_destroy(nfai_batch_t batch);
 /* ≙ one pass of the loop body LlamaModel.cs:116-125 for every member: tokens[i] is embedded, runs through every block at member

@@ -1934,7 +1934,8 @@ struct Batch {
     Model *mem[BATCH_MAX] = {};
     uint64_t serial[BATCH_MAX] = {};
     uint32_t gen[BATCH_MAX] = {};
-    uint32_t *d_tok = nullptr;     // [0..7] token words (in: the step's tokens, out: the ArgMax), [8] error word
+    bool quant = false;            // the members' matrices are Q4_K / Q6_K in the T16 layout (nfai_hip_llama_batch_create_ex, NFAI_BATCH_QUANT)
+    uint32_t *d_tok = nullptr;    // [0..7] token words (in: the step's tokens, out: the ArgMax), [8] error word
     void *d_am = nullptr, *d_attn = nullptr;
     uint32_t *h_pin = nullptr;     // [0..7] tokens in | [16..24] token words + error word out
     hipGraph_t g_step = nullptr, g_body = nullptr;
@@ -2055,6 +2056,34 @@ struct BatchOps {
     }
 };
 
+// Quantised members (NFAI_BATCH_QUANT): the same launch arguments over T16 tensors (kernels_gemv_batch_kqm.hip).
+BatchKqArgs batch_kq(const BatchGemvArgs &a, int type)
+{
+    BatchKqArgs k;
+    static_cast<BatchGemvArgs &>(k) = a;
+    k.w_type = type;
+    return k;
+}
+
+// q|k|v of block l by weight type: one launch when the three matrices agree, two when they differ (Q4_K_M files keep attn_v in Q6_K
+// on half of the blocks), so that a launch stages the activations in ONE fragment layout.  Returns the number of launches.
+int batch_qkv_kq(const BatchOps &ops, size_t l, BatchKqArgs (&out)[2])
+{
+    const BatchGemvArgs base = ops.qkv(l);
+    const Layer &L = ops.bt->mem[0]->layers[l];
+    const Tensor *t[3] = {&L.wq, &L.wk, &L.wv};
+    int n = 0;
+    for (int type : {NFAI_Q4_K_T16, NFAI_Q6_K_T16}) {
+        BatchKqArgs k = batch_kq(base, type);
+        int j = 0;
+        for (int i = 0; i < 3; i++) { k.W[i] = nullptr; k.seg_rows[i] = 0; }
+        for (int i = 0; i < 3; i++)
+            if (t[i]->type == type) { k.W[j] = t[i]->ptr; k.seg_rows[j] = (uint32_t)t[i]->rows; k.seg_role[j] = (uint32_t)i; j++; }
+        if (j) out[n++] = k;
+    }
+    return n;
+}
+
 // One token of every member, enqueued on the stream.  ms / cnt (profiling, both or neither): hipEvents around every launch, by class.
 int enqueue_batch(Batch *bt, float *ms = nullptr, uint32_t *cnt = nullptr)
 {
@@ -2080,15 +2109,30 @@ int enqueue_batch(Batch *bt, float *ms = nullptr, uint32_t *cnt = nullptr)
 #define B_TRY(c, expr) S_TRY(run(c, [&]() -> hipError_t { return (expr); }))
     float *xs[BATCH_MAX] = {};
     for (uint32_t i = 0; i < bt->n; i++) xs[i] = bt->mem[i]->x;
-    B_TRY(KC_OTHER, launch_batch_embed(m0->token_embd.ptr, m0->token_embd.rows, m0->d.E, bt->d_tok, xs, bt->n, s));
-    for (size_t l = 0; l < m0->layers.size(); l++) {
-        B_TRY(KC_QKV, launch_batch_gemv(ops.qkv(l), s));
-        B_TRY(KC_ATTN, launch_batch_attn(ops.attn(l), s));
-        B_TRY(KC_WO, launch_batch_gemv(ops.wo(l), s));
-        B_TRY(KC_GATEUP, launch_batch_gemv(ops.gateup(l), s));
-        B_TRY(KC_DOWN, launch_batch_gemv(ops.down(l), s));
+    if (bt->quant) {   // 5 launches per block, 6 where q|k|v is split by type
+        B_TRY(KC_OTHER, launch_batch_embed_kq(m0->token_embd.ptr, m0->token_embd.type, m0->token_embd.rows, m0->d.E, bt->d_tok, xs, bt->n, s));
+        for (size_t l = 0; l < m0->layers.size(); l++) {
+            const Layer &L = m0->layers[l];
+            BatchKqArgs qkv[2];
+            const int nq = batch_qkv_kq(ops, l, qkv);
+            for (int j = 0; j < nq; j++) B_TRY(KC_QKV, launch_batch_gemv_kq(qkv[j], s));
+            B_TRY(KC_ATTN, launch_batch_attn(ops.attn(l), s));
+            B_TRY(KC_WO, launch_batch_gemv_kq(batch_kq(ops.wo(l), L.wo.type), s));
+            B_TRY(KC_GATEUP, launch_batch_gemv_kq(batch_kq(ops.gateup(l), L.wgate.type), s));
+            B_TRY(KC_DOWN, launch_batch_gemv_kq(batch_kq(ops.down(l), L.wdown.type), s));
+        }
+        B_TRY(KC_LMHEAD, launch_batch_gemv_kq(batch_kq(ops.head(), (m0->output.ptr ? m0->output : m0->token_embd).type), s));
+    } else {
+        B_TRY(KC_OTHER, launch_batch_embed(m0->token_embd.ptr, m0->token_embd.rows, m0->d.E, bt->d_tok, xs, bt->n, s));
+        for (size_t l = 0; l < m0->layers.size(); l++) {
+            B_TRY(KC_QKV, launch_batch_gemv(ops.qkv(l), s));
+            B_TRY(KC_ATTN, launch_batch_attn(ops.attn(l), s));
+            B_TRY(KC_WO, launch_batch_gemv(ops.wo(l), s));
+            B_TRY(KC_GATEUP, launch_batch_gemv(ops.gateup(l), s));
+            B_TRY(KC_DOWN, launch_batch_gemv(ops.down(l), s));
+        }
+        B_TRY(KC_LMHEAD, launch_batch_gemv(ops.head(), s));
     }
-    B_TRY(KC_LMHEAD, launch_batch_gemv(ops.head(), s));
 #undef B_TRY
     if (ms) {
         HIP_TRY(hipStreamSynchronize(s));
@@ -2157,46 +2201,70 @@ int batch_device_failed(Batch *bt, uint32_t code, const char *fn)
 
 }  // namespace
 
-NFAI_API int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_t n, nfai_batch_t *out)
+// fn: the entry point's name in messages.  flags: NFAI_BATCH_* (0 = the fp16 batch of nfai_hip_llama_batch_create).
+static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out, const char *fn)
 {
-    if (!models || !out) return fail(NFAI_ERR_INVALID, "batch_create: null argument");
-    if (n < 1 || n > BATCH_MAX) return fail(NFAI_ERR_INVALID, "batch_create: invalid n = %u (a batch holds 1 to %u models)", n, BATCH_MAX);
+    if (!models || !out) return fail(NFAI_ERR_INVALID, "%s: null argument", fn);
+    if (flags & ~(uint32_t)NFAI_BATCH_QUANT) return fail(NFAI_ERR_INVALID, "%s: invalid flags 0x%x (known: NFAI_BATCH_QUANT = 0x%x)", fn, flags, NFAI_BATCH_QUANT);
+    bool quant = false;
+    if (n < 1 || n > BATCH_MAX) return fail(NFAI_ERR_INVALID, "%s: invalid n = %u (a batch holds 1 to %u models)", fn, n, BATCH_MAX);
     Model *mem[BATCH_MAX] = {};
     for (uint32_t i = 0; i < n; i++) {
         mem[i] = model_of(models[i]);
-        if (!mem[i]) return fail(NFAI_ERR_INVALID, "batch_create: member %u: invalid model handle", i);
+        if (!mem[i]) return fail(NFAI_ERR_INVALID, "%s: member %u: invalid model handle", fn, i);
         for (uint32_t j = 0; j < i; j++)
-            if (mem[j] == mem[i]) return fail(NFAI_ERR_INVALID, "batch_create: invalid member %u: the same model as member %u", i, j);
+            if (mem[j] == mem[i]) return fail(NFAI_ERR_INVALID, "%s: invalid member %u: the same model as member %u", fn, i, j);
     }
     Model *m0 = mem[0];
     for (uint32_t i = 0; i < n; i++)
-        if (mem[i]->ctx != m0->ctx) return fail(NFAI_ERR_INVALID, "batch_create: invalid member %u: it lives on another context than member 0", i);
+        if (mem[i]->ctx != m0->ctx) return fail(NFAI_ERR_INVALID, "%s: invalid member %u: it lives on another context than member 0", fn, i);
     HIP_TRY(hipSetDevice(m0->ctx->device));
     for (uint32_t i = 0; i < n; i++) {
         Model *m = mem[i];
-        if (!m->finalized) return fail(NFAI_ERR_INVALID, "batch_create: invalid member %u: call nfai_hip_llama_finalize first", i);
+        if (!m->finalized) return fail(NFAI_ERR_INVALID, "%s: invalid member %u: call nfai_hip_llama_finalize first", fn, i);
         if (!(m->first_stage && m->last_stage))
-            return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member %u is a pipeline stage (blocks [%u, %u) of %u); a batch takes whole models", i,
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u is a pipeline stage (blocks [%u, %u) of %u); a batch takes whole models", fn, i,
                         m->d.layer_begin, m->d.layer_end, m->d.L);
         if (m->unfused || m->engine)
-            return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member %u runs the %s path; a batch takes models of the fused five-launch path", i,
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u runs the %s path; a batch takes models of the fused five-launch path", fn, i,
                         m->unfused ? "1:1 (NFAI_LLAMA_UNFUSED)" : "engine");
         if (m->kv_f16 != m0->kv_f16)
-            return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member %u keeps an %s KV cache, member 0 an %s one; one element type per batch", i,
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u keeps an %s KV cache, member 0 an %s one; one element type per batch", fn, i,
                         m->kv_f16 ? "fp16" : "fp32", m0->kv_f16 ? "fp16" : "fp32");
-        auto f16 = [&](const Tensor &t, const char *what, size_t blk) -> int {
-            if (t.ptr && t.type != NFAI_F16)
-                return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member %u: %s of block %zu has ggml type %d; the batched kernels take fp16 matrices "
-                                                  "(K-quant and Q8_0 weights decode through nfai_hip_llama_decode_step)", i, what, blk, ggml_type_of(t.type));
+        // matrix types: fp16 throughout, or (NFAI_BATCH_QUANT) Q4_K / Q6_K in the T16 layout throughout, in any per-tensor mix
+        const bool allow_q = (flags & NFAI_BATCH_QUANT) != 0;
+        const char *first16 = nullptr, *firstq = nullptr;
+        size_t first16_blk = 0, firstq_blk = 0;
+        int firstq_type = 0;
+        auto mat = [&](const Tensor &t, const char *what, size_t blk) -> int {
+            if (!t.ptr) return NFAI_OK;
+            if (t.type == NFAI_F16) {
+                if (!first16) { first16 = what; first16_blk = blk; }
+                return NFAI_OK;
+            }
+            if (!allow_q)
+                return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u: %s of block %zu has ggml type %d; the batched kernels take fp16 matrices "
+                                                  "(K-quant and Q8_0 weights decode through nfai_hip_llama_decode_step)", fn, i, what, blk, ggml_type_of(t.type));
+            if (t.type == NFAI_Q4_K || t.type == NFAI_Q6_K)
+                return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u: %s of block %zu (ggml type %d, %llu rows) runs the VALU fallback (rows %% 16 != 0); the batched "
+                                                  "int8-MFMA kernels take 16-row tiles", fn, i, what, blk, ggml_type_of(t.type), (unsigned long long)t.rows);
+            if (t.type != NFAI_Q4_K_T16 && t.type != NFAI_Q6_K_T16)
+                return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u: %s of block %zu has ggml type %d; a quantised batch takes Q4_K and Q6_K matrices "
+                                                  "(Q5_K and Q8_0 weights decode through nfai_hip_llama_decode_step)", fn, i, what, blk, ggml_type_of(t.type));
+            if (!firstq) { firstq = what; firstq_blk = blk; firstq_type = ggml_type_of(t.type); }
             return NFAI_OK;
         };
-        S_TRY(f16(m->token_embd, "token_embd", 0));
-        S_TRY(f16(m->output, "output", 0));
+        S_TRY(mat(m->token_embd, "token_embd", 0));
+        S_TRY(mat(m->output, "output", 0));
         for (size_t l = 0; l < m->layers.size(); l++) {
             const Layer &L = m->layers[l];
-            S_TRY(f16(L.wq, "attn_q", l)); S_TRY(f16(L.wk, "attn_k", l)); S_TRY(f16(L.wv, "attn_v", l)); S_TRY(f16(L.wo, "attn_output", l));
-            S_TRY(f16(L.wgate, "ffn_gate", l)); S_TRY(f16(L.wup, "ffn_up", l)); S_TRY(f16(L.wdown, "ffn_down", l));
+            S_TRY(mat(L.wq, "attn_q", l)); S_TRY(mat(L.wk, "attn_k", l)); S_TRY(mat(L.wv, "attn_v", l)); S_TRY(mat(L.wo, "attn_output", l));
+            S_TRY(mat(L.wgate, "ffn_gate", l)); S_TRY(mat(L.wup, "ffn_up", l)); S_TRY(mat(L.wdown, "ffn_down", l));
         }
+        if (first16 && firstq)
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u mixes fp16 and quantised matrices (%s of block %zu is fp16, %s of block %zu has ggml type %d); "
+                                              "a batch runs one kernel family", fn, i, first16, first16_blk, firstq, firstq_blk, firstq_type);
+        quant = firstq != nullptr;   // (every member reads member 0's tensors, checked below)
         // the same tensors as member 0: a donor and models that called nfai_hip_llama_share_tensors on it, in any order
         bool same = m->layers.size() == m0->layers.size() && m->token_embd.ptr == m0->token_embd.ptr && m->output.ptr == m0->output.ptr &&
                     m->output_norm.ptr == m0->output_norm.ptr && m->d.E == m0->d.E && m->d.H == m0->d.H && m->d.Hkv == m0->d.Hkv &&
@@ -2208,26 +2276,40 @@ NFAI_API int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_
                    A.ffn_norm.ptr == B.ffn_norm.ptr && A.wgate.ptr == B.wgate.ptr && A.wup.ptr == B.wup.ptr && A.wdown.ptr == B.wdown.ptr;
         }
         if (!same)
-            return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member %u does not read the same tensors as member 0 (one copy of the weights per batch: "
-                                              "nfai_hip_llama_share_tensors)", i);
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u does not read the same tensors as member 0 (one copy of the weights per batch: "
+                                              "nfai_hip_llama_share_tensors)", fn, i);
     }
-    if (!m0->token_embd.ptr) return fail(NFAI_ERR_UNSUPPORTED, "batch_create: member 0 has no token embedding");
+    if (!m0->token_embd.ptr) return fail(NFAI_ERR_UNSUPPORTED, "%s: member 0 has no token embedding", fn);
     Batch *bt = new Batch();
     bt->ctx = m0->ctx;
     bt->n = n;
+    bt->quant = quant;
     for (uint32_t i = 0; i < n; i++) { bt->handles[i] = models[i]; bt->mem[i] = mem[i]; bt->serial[i] = mem[i]->serial; bt->gen[i] = mem[i]->weights_gen; }
     // shapes the batched kernels take (nothing is allocated before this is known)
     {
         BatchOps ops{bt};
         uint32_t dummy = 0;
         bt->d_tok = &dummy; bt->d_am = &dummy; bt->d_attn = &dummy;   // placeholders for the argument checks only
-        const bool ok = batch_gemv_ok(ops.qkv(0)) && batch_gemv_ok(ops.wo(0)) && batch_gemv_ok(ops.gateup(0)) && batch_gemv_ok(ops.down(0)) &&
-                        batch_gemv_ok(ops.head()) && attn_group_ok(m0->d.H / m0->d.Hkv);
+        bool ok = attn_group_ok(m0->d.H / m0->d.Hkv);
+        if (quant) {   // per block: the types, and with them the q|k|v split and the LDS of a launch, differ from block to block
+            for (size_t l = 0; ok && l < m0->layers.size(); l++) {
+                const Layer &L = m0->layers[l];
+                BatchKqArgs qkv[2];
+                const int nq = batch_qkv_kq(ops, l, qkv);
+                for (int j = 0; j < nq; j++) ok = ok && batch_gemv_kq_ok(qkv[j]);
+                ok = ok && L.wgate.type == L.wup.type && batch_gemv_kq_ok(batch_kq(ops.wo(l), L.wo.type)) &&
+                     batch_gemv_kq_ok(batch_kq(ops.gateup(l), L.wgate.type)) && batch_gemv_kq_ok(batch_kq(ops.down(l), L.wdown.type));
+            }
+            ok = ok && m0->d.E % 256 == 0 && batch_gemv_kq_ok(batch_kq(ops.head(), (m0->output.ptr ? m0->output : m0->token_embd).type));
+        } else {
+            ok = ok && batch_gemv_ok(ops.qkv(0)) && batch_gemv_ok(ops.wo(0)) && batch_gemv_ok(ops.gateup(0)) && batch_gemv_ok(ops.down(0)) &&
+                 batch_gemv_ok(ops.head());
+        }
         bt->d_tok = nullptr; bt->d_am = nullptr; bt->d_attn = nullptr;
         if (!ok) {
             const nfai_llama_desc &d = m0->d;
             delete bt;
-            return fail(NFAI_ERR_UNSUPPORTED, "batch_create: the batched kernels do not take this shape at n = %u (E %u, F %u, H %u, Hkv %u, D %u, V %u)", n,
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: the batched kernels do not take this shape at n = %u (E %u, F %u, H %u, Hkv %u, D %u, V %u)", fn, n,
                         d.E, d.F, d.H, d.Hkv, d.D, d.V);
         }
     }
@@ -2236,12 +2318,22 @@ NFAI_API int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_
     if ((rc = dalloc(reinterpret_cast<void **>(&bt->d_tok), 256, bt->ctx->stream))) return bail(rc);
     if ((rc = dalloc(&bt->d_am, batch_argmax_bytes(), bt->ctx->stream))) return bail(rc);
     if ((rc = dalloc(&bt->d_attn, batch_attn_bytes(m0->d.H, m0->d.D), bt->ctx->stream))) return bail(rc);
-    if (hipHostMalloc(reinterpret_cast<void **>(&bt->h_pin), 256, hipHostMallocDefault) != hipSuccess) return bail(fail(NFAI_ERR_OOM, "batch_create: pinned staging"));
+    if (hipHostMalloc(reinterpret_cast<void **>(&bt->h_pin), 256, hipHostMallocDefault) != hipSuccess) return bail(fail(NFAI_ERR_OOM, "%s: pinned staging", fn));
     memset(bt->h_pin, 0, 256);
-    if (hipStreamSynchronize(bt->ctx->stream) != hipSuccess) return bail(fail(NFAI_ERR_HIP, "batch_create: stream synchronisation failed"));
+    if (hipStreamSynchronize(bt->ctx->stream) != hipSuccess) return bail(fail(NFAI_ERR_HIP, "%s: stream synchronisation failed", fn));
     handle_register(bt);
     *out = reinterpret_cast<nfai_batch_t>(bt);
     return NFAI_OK;
+}
+
+NFAI_API int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_t n, nfai_batch_t *out)
+{
+    return batch_create_impl(models, n, 0, out, "batch_create");
+}
+
+NFAI_API int32_t nfai_hip_llama_batch_create_ex(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out)
+{
+    return batch_create_impl(models, n, flags, out, "batch_create_ex");
 }
 
 NFAI_API int32_t nfai_hip_llama_batch_destroy(nfai_batch_t h)
@@ -2339,9 +2431,13 @@ NFAI_API int32_t nfai_hip_llama_batch_bytes_per_token(nfai_batch_t h, uint64_t *
     for (const Layer &L : m0->layers)   // every weight byte once per step (W + n KV(p))
         t += tensor_bytes(L.wq) + tensor_bytes(L.wk) + tensor_bytes(L.wv) + tensor_bytes(L.wo) + tensor_bytes(L.wgate) + tensor_bytes(L.wup) + tensor_bytes(L.wdown);
     t += tensor_bytes(m0->output.ptr ? m0->output : m0->token_embd);
+    if (bt->quant) {   // every T16 plane once (a tied token_embd is the head's), and the norm gains every normed launch reads
+        for (const Layer &L : m0->layers) t += tensor_bytes(L.attn_norm) + tensor_bytes(L.ffn_norm);
+        t += tensor_bytes(m0->output_norm);
+    }
     for (uint32_t i = 0; i < bt->n; i++) {   // per member: its embedding row, its KV rows read (p + 1 positions) and written (1)
         Model *m = bt->mem[i];
-        t += weight_row_bytes(m0->token_embd.type, d.E);
+        if (!bt->quant || m0->output.ptr) t += weight_row_bytes(m0->token_embd.type, d.E);
         t += (uint64_t)m0->layers.size() * (2ull * d.Hkv * d.D * m->kv_esz * ((uint64_t)m->pos_host + 1) + 2ull * d.Hkv * d.D * m->kv_esz);
     }
     if (total) *total = t;

@@ -328,16 +328,20 @@ class LlamaModel:
 
 class LlamaBatch:
     """n LlamaModel instances over ONE set of weights advancing together: what n concurrent token loops (LlamaModel.cs:116-125) do,
-    with every weight row read once per step (nfai_hip_llama_batch_*).  `models`: 1 to 8 whole fp16 models on one buffer manager,
+    with every weight row read once per step (nfai_hip_llama_batch_*).  `models`: 1 to 8 whole fp16 models (quantized=True: or
+    1 to 8 whole models whose matrices are all Q4_K / Q6_K) on one buffer manager,
     one of them the donor of the others (`share_from`).  Each member keeps its own KV cache and position and stays a normal
     LlamaModel: Step / Ingest / SetPos on a member between batch steps are seen by the next batch step."""
 
-    def __init__(self, models):
+    def __init__(self, models, quantized: bool = False):
         self.models = list(models)
         self.n = len(self.models)
         hs = (_lib.H * max(self.n, 1))(*[m.handle.value if isinstance(m.handle, _lib.H) else int(m.handle) for m in self.models])
         h = _lib.H()
-        call("nfai_hip_llama_batch_create", hs, self.n, C.byref(h))
+        if quantized:   # also admits members whose matrices are all Q4_K / Q6_K (Q4_K_M files): the int8-MFMA batch
+            call("nfai_hip_llama_batch_create_ex", hs, self.n, _lib.BATCH_QUANT, C.byref(h))
+        else:
+            call("nfai_hip_llama_batch_create", hs, self.n, C.byref(h))
         self.handle = h
         self.V = int(self.models[0].dims["V"])
 

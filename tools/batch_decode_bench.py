@@ -16,6 +16,11 @@ algorithmic bytes and fraction of the HBM roofline.  Parity: max |dlogit| of the
 the oracle, which takes about a minute of host time).  One JSON line; --out writes it to a file too.
 
     python tools/batch_decode_bench.py --out profiles/batch_decode.json
+    python tools/batch_decode_bench.py --quant q4_k_m --out profiles/batch_decode_q4_k_m.json
+
+--quant q4_k_m: the same run on llama.cpp's Q4_K_M tensor mix (bench.gen_weights_hbm's random K-quant super-blocks; Q4_K with Q6_K
+for token_embd / output and for attn_v / ffn_down of the blocks llama.cpp keeps there), through the int8-MFMA batch
+(LlamaBatch(..., quantized=True), nfai_hip_llama_batch_create_ex); the oracle walks the dequantised weights.
 """
 import argparse
 import json
@@ -46,19 +51,19 @@ def class_bytes(weights, dims, positions, kv_esz=4):
     head = "output.weight" if "output.weight" in weights else "token_embd.weight"
     return {"qkv": avg("attn_q", "attn_k", "attn_v") + n * 2 * KD * kv_esz, "attn": sum(2 * KD * kv_esz * (p + 1) for p in positions),
             "wo": avg("attn_output"), "gateup": avg("ffn_gate", "ffn_up"), "down": avg("ffn_down"), "lmhead": wb(head),
-            "other": n * dims.E * 2}
+            "other": n * wb("token_embd.weight") // weights["token_embd.weight"][2]}
 
 
 def spread(xs):
     return (max(xs) - min(xs)) / statistics.median(xs)
 
 
-def run_model(torch, dims, steps, windows):
+def run_model(torch, dims, steps, windows, quant="f16"):
     import bench as B
     from nfai_amd import synth
     from nfai_amd.hip import HipBufferManager
     from nfai_amd.llama_model import LlamaBatch, LlamaModel
-    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant="f16")
+    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant=quant)
     C = T + WARM + steps + 16
     mgr = HipBufferManager(0)
     dd = dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0)
@@ -82,10 +87,10 @@ def run_model(torch, dims, steps, windows):
         for m in ms:
             m.SetPos(p0)
 
-    out = {"model": dims.name, "weights": "f16", "kv_cache": "f32", "positions": [p0, p0 + steps - 1], "steps_per_window": steps, "by_n": {}}
+    out = {"model": dims.name, "weights": quant, "kv_cache": "f32", "positions": [p0, p0 + steps - 1], "steps_per_window": steps, "by_n": {}}
     for n in (1, 2, 4, 8):
         ms = members[:n]
-        batch = LlamaBatch(ms)
+        batch = LlamaBatch(ms, quantized=quant != "f16")
 
         def batch_window():
             rewind(ms)
@@ -166,14 +171,14 @@ def run_model(torch, dims, steps, windows):
     return out
 
 
-def oracle_parity(torch, dims, n=4):
+def oracle_parity(torch, dims, n=4, quant="f16"):
     """n = 4 on full-size weights at shallow staggered depths (the oracle walks every earlier token on the host): max |dlogit| over 4 steps."""
     import bench as B
     import oracle as orc
     from nfai_amd import synth
     from nfai_amd.hip import HipBufferManager
     from nfai_amd.llama_model import LlamaBatch, LlamaModel
-    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant="f16")
+    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant=quant)
     C = 32
     mgr = HipBufferManager(0)
     dd = dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0)
@@ -182,7 +187,7 @@ def oracle_parity(torch, dims, n=4):
     ms = [LlamaModel(mgr, md, wt, C, dims=dd)]
     for _ in range(1, n):
         ms.append(LlamaModel(mgr, md, wt, C, dims=dd, share_from=ms[0]))
-    host = {k: t.cpu().numpy() for k, (t, ty, r, c) in weights.items()}
+    host = B.host_weights(weights)   # K-quant matrices dequantised
     toks = [synth.make_tokens(dims, 24, seed=400 + s) for s in range(n)]
     refs = []
     for s in range(n):
@@ -191,7 +196,7 @@ def oracle_parity(torch, dims, n=4):
             ms[s].Step(int(t), want_logits=False)
             ref.step(int(t), want_logits=False)
         refs.append(ref)
-    batch = LlamaBatch(ms)
+    batch = LlamaBatch(ms, quantized=quant != "f16")
     worst, top, same = 0.0, 0.0, []
     for i in range(4):
         st = [int(toks[s][2 + 3 * s + i]) for s in range(n)]
@@ -205,7 +210,7 @@ def oracle_parity(torch, dims, n=4):
     for m in reversed(ms):
         m.Dispose()
     mgr.Dispose()
-    return {"model": dims.name, "n": n, "positions_of_member_0": [2, 5], "max_abs_logit_diff": worst, "max_abs_logit": top, "argmax_equal": same}
+    return {"model": dims.name, "weights": quant, "n": n, "positions_of_member_0": [2, 5], "max_abs_logit_diff": worst, "max_abs_logit": top, "argmax_equal": same}
 
 
 def main():
@@ -214,19 +219,20 @@ def main():
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--only", default="", metavar="MODEL", help="one model, e.g. llama-3.2-3b")
+    ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m"], help="weight encoding (q4_k_m: the int8-MFMA batch)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     from nfai_amd import synth
     torch.cuda.set_device(0)
-    out = {"tool": "batch_decode_bench", "models": []}
+    out = {"tool": "batch_decode_bench", "weights": a.quant, "models": []}
     for dims in (synth.LLAMA_32_3B, synth.LLAMA_32_1B):
         if a.only and a.only != dims.name:
             continue
-        out["models"].append(run_model(torch, dims, a.steps, max(3, a.windows)))
+        out["models"].append(run_model(torch, dims, a.steps, max(3, a.windows), a.quant))
         torch.cuda.empty_cache()
     if not a.no_check:
-        out["parity_vs_oracle"] = oracle_parity(torch, synth.LLAMA_32_1B)
+        out["parity_vs_oracle"] = oracle_parity(torch, synth.LLAMA_32_1B, quant=a.quant)
     line = json.dumps(out)
     print(line)
     if a.out:
