@@ -92,13 +92,13 @@ uint64_t weight_row_bytes(int t, uint64_t n_cols)
         case NFAI_F32: return n_cols * 4;
         case NFAI_F16: return n_cols % 8 == 0 ? n_cols * 2 : 0;
         case NFAI_Q4_K:
-        case NFAI_Q4_K_T16: return n_cols % 256 == 0 ? n_cols / 256 * 144 : 0;
+        case NFAI_Q4_K_T16: return n_cols % 256 == 0 ? n_cols / 256 * GGML_Q4_K_BLOCK : 0;
         case NFAI_Q6_K:
-        case NFAI_Q6_K_T16: return n_cols % 256 == 0 ? n_cols / 256 * 210 : 0;
+        case NFAI_Q6_K_T16: return n_cols % 256 == 0 ? n_cols / 256 * GGML_Q6_K_BLOCK : 0;
         case NFAI_Q8_0:
-        case NFAI_Q8_0_T16: return n_cols % 256 == 0 && n_cols <= 32768 ? n_cols / 32 * 34 : 0;  // the int8-MFMA GEMV's K rules
+        case NFAI_Q8_0_T16: return n_cols % 256 == 0 && n_cols <= 32768 ? n_cols / 32 * GGML_Q8_0_BLOCK : 0;  // the int8-MFMA GEMV's K rules
         case NFAI_Q5_K:
-        case NFAI_Q5_K_T16: return n_cols % 256 == 0 && n_cols <= 32768 ? n_cols / 256 * 176 : 0;  // (same rules)
+        case NFAI_Q5_K_T16: return n_cols % 256 == 0 && n_cols <= 32768 ? n_cols / 256 * GGML_Q5_K_BLOCK : 0;  // (same rules)
     }
     return 0;
 }

@@ -138,7 +138,7 @@ struct GemvArgs {
 constexpr size_t argmax_fused_bytes() { return 1024 * 8 + 256; }  // [1024] values | [1024] indices | ticket
 enum GemvMode { GEMV_PLAIN = 0, GEMV_RESIDUAL = 1, GEMV_QKV_ROPE = 2, GEMV_GATEUP = 3 };
 
-// Internal weight-type codes of the T16 layouts (kernels_gemv_kqm.hip): same bytes as the ggml type, rows
+// Internal weight-type codes of the T16 layouts (t16.h): same bytes as the ggml type, rows
 // grouped in tiles of 16.  Never seen across the C ABI: uploads with rows % 16 == 0 are repacked into them.
 // Q8_0 and Q5_K exist only in the T16 layout (rows % 16 == 0 is a rule of their upload); is_kquant covers them (block-quantised,
 // same paths).
@@ -496,6 +496,17 @@ __device__ __forceinline__ float dot8_f16(u32x4 w, f32x4 x0, f32x4 x1, float acc
     return acc;
 }
 
+// one element of a KV cache (fp16 or fp32 per the model's kv_type)
+__device__ __forceinline__ void kv_store(void *base, int f16, uint64_t idx, float v)
+{
+    if (f16) reinterpret_cast<_Float16 *>(base)[idx] = (_Float16)v;
+    else reinterpret_cast<float *>(base)[idx] = v;
+}
+
+}  // namespace nfai
+#include "t16.h"  // the T16 layout of quantised tensors: plane addresses and block decode (uses the types and loads above)
+namespace nfai {
+
 // ---- the per-token prologue inside the first q|k|v launch (GemvArgs::Begin) -------------------------------------------------------
 struct BeginParams {
     const uint8_t *emb;
@@ -511,7 +522,7 @@ struct BeginParams {
 };
 
 // four consecutive elements k .. k+3 (k % 4 == 0) of row `row` of an embedding table with E columns, widened to fp32 exactly as
-// TokenEmbedShader (TokenEmbedShader.cs:131-159) / k_embed_q4t / k_embed_q5t / k_embed_q6t / k_embed_q8t give them
+// TokenEmbedShader (TokenEmbedShader.cs:131-159) gives them; a quantised table is in the T16 layout (t16_row_load4)
 __device__ __forceinline__ f32x4 embed_load4(const uint8_t *table, int type, uint64_t n_rows, uint64_t row, uint32_t k, uint32_t E)
 {
     typedef __attribute__((address_space(1))) uint8_t g8;
@@ -521,51 +532,7 @@ __device__ __forceinline__ f32x4 embed_load4(const uint8_t *table, int type, uin
         return f32x4{h2f_lo(w[0]), h2f_hi(w[0]), h2f_lo(w[1]), h2f_hi(w[1])};
     }
     if (type == NFAI_F32) return *reinterpret_cast<const __attribute__((address_space(1))) f32x4 *>(t + (row * E + k) * 4);
-    const uint32_t NB = E / 256, blk = k >> 8, kk = k & 255;
-    const uint64_t tile = row >> 4, r = row & 15, tb = tile * NB + blk, nblk = n_rows * NB;
-    f32x4 out;
-    if (type == NFAI_Q8_0_T16) {  // k_embed_q8t
-        const uint32_t ln = ((kk >> 4) & 3) * 16 + (uint32_t)r;
-        const uint32_t q4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t + tb * 4096 + (kk >> 6) * 1024 + ln * 16 + (kk & 15));
-        const uint32_t b32 = kk >> 5;  // its d: half (b32 & 1) * 4 + (b32 >> 1) of the row's 16 bytes
-        const float d = (float)reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(t + nblk * 256 + tb * 256 + r * 16)[(b32 & 1) * 4 + (b32 >> 1)];
-#pragma unroll
-        for (int e = 0; e < 4; e++) out[e] = d * (float)(int8_t)((q4 >> (8 * e)) & 0xFFu);
-    } else if (type == NFAI_Q4_K_T16 || type == NFAI_Q5_K_T16) {  // k_embed_q4t / k_embed_q5t
-        const uint32_t sb = kk >> 5, l = kk & 31;
-        const g8 *hdr = t + nblk * 128 + tb * 256 + r * 16;
-        const float d = (float)*reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(hdr);
-        const float dmin = (float)*reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(hdr + 2);
-        const g8 *scales = hdr + 4;
-        uint32_t sc, m;
-        if (sb < 4) { sc = scales[sb] & 63; m = scales[sb + 4] & 63; }
-        else { sc = (scales[sb + 4] & 0xF) | ((scales[sb - 4] >> 6) << 4); m = (scales[sb + 4] >> 4) | ((scales[sb] >> 6) << 4); }
-        const uint32_t q4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t + tb * 2048 + (l >> 4) * 1024 + ((sb >> 1) * 16 + r) * 16 + (l & 15));
-        uint32_t h5 = 0;  // Q5_K: the fifth bits of the four weights at bits 8e of h5 (high-bit plane, k_repack_q5k_t16)
-        if (type == NFAI_Q5_K_T16)
-            h5 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t + nblk * 144 + tb * 512 + ((sb >> 1) * 16 + r) * 8 + (l >> 4) * 4) >>
-                 (4 * (sb & 1) + ((l >> 2) & 3));
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const uint32_t q = (q4 >> (8 * e)) & 0xFFu;
-            const uint32_t q5 = ((sb & 1) ? (q >> 4) : (q & 0xF)) | (((h5 >> (8 * e)) & 1u) << 4);
-            out[e] = d * (float)sc * (float)q5 - dmin * (float)m;
-        }
-    } else {  // NFAI_Q6_K_T16: k_embed_q6t
-        const uint32_t n = kk >> 7, qd = (kk >> 5) & 3, l = kk & 31, lh = l >> 4, b = l & 15;
-        const uint32_t ln = (n * 2 + lh) * 16 + (uint32_t)r;
-        const uint32_t ql4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t + tb * 3072 + (qd & 1) * 1024 + ln * 16 + b);
-        const uint32_t qh4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t + tb * 3072 + 2048 + ln * 16 + b);
-        const int sc = (int)(int8_t)t[nblk * 192 + tb * 256 + r * 16 + 8 * n + lh + 2 * qd];
-        const float d = (float)reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(t + nblk * 208 + tb * 32)[r];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const uint32_t ql = (ql4 >> (8 * e)) & 0xFFu, qh = (qh4 >> (8 * e)) & 0xFFu;
-            const int q = (int)(((qd >= 2) ? (ql >> 4) : (ql & 0xF)) | (((qh >> (2 * qd)) & 3) << 4)) - 32;
-            out[e] = d * (float)sc * (float)q;
-        }
-    }
-    return out;
+    return t16_row_load4(table, type, n_rows, row, k, E);
 }
 
 // cos / sin of RoPE pair `pair` at position pos, as k_token_begin tabulates them (RoPEShader.cs:254-256)

@@ -121,12 +121,6 @@ __device__ __forceinline__ const uint8_t *row_ptr(const GemvParams &p, uint32_t 
     }
 }
 
-__device__ __forceinline__ void kv_store(void *base, int f16, uint64_t idx, float v)
-{
-    if (f16) reinterpret_cast<_Float16 *>(base)[idx] = (_Float16)v;
-    else reinterpret_cast<float *>(base)[idx] = v;
-}
-
 // What the epilogue of `unit` will read from memory, requested when the unit's first K step is
 // consumed so the latency is hidden behind the rest of the row (a load issued in the epilogue
 // itself would add a full memory round trip to every short kernel).  Unconditional, clamped.

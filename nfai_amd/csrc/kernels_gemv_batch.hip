@@ -88,12 +88,6 @@ __device__ __forceinline__ const uint8_t *bg_row_ptr(const BGemvParams &p, uint3
     }
 }
 
-__device__ __forceinline__ void bg_kv_store(void *base, int f16, uint64_t idx, float v)
-{
-    if (f16) reinterpret_cast<_Float16 *>(base)[idx] = (_Float16)v;
-    else reinterpret_cast<float *>(base)[idx] = v;
-}
-
 // What a lane needs to finish rows of ITS column (the column is a function of the lane, see bg_reduce): selected once per launch.
 struct BGLane {
     float *y;
@@ -133,8 +127,8 @@ __device__ __forceinline__ void bg_epilogue(const BGemvParams &p, const BGLane &
         } else if (c.pos_ok) {   // a position word at or past the capacity writes nothing (the launch reports it through p.err)
             const uint64_t idx = (uint64_t)c.pos * p.pos_stride + (uint64_t)head * c.head_stride + d;
             void *base = seg == 1 ? c.kc : c.vc;
-            bg_kv_store(base, p.kv_f16, idx, o0);
-            bg_kv_store(base, p.kv_f16, idx + 1, o1);
+            kv_store(base, p.kv_f16, idx, o0);
+            kv_store(base, p.kv_f16, idx + 1, o1);
         }
     }
 }

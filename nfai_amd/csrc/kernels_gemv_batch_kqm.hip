@@ -2,7 +2,8 @@
 // quantised weight row is read from HBM ONCE, unpacked ONCE and multiplied on the matrix cores with the fixed-point activations of up to
 // 8 sequences (MatrixMultiplyShader.cs:255-289 at M = B on weights the reference cannot load, Parser.cs:111-114; the prologues and
 // epilogues of TransformerBlock.Compute, TransformerBlock.cs:127-184, per column as in k_bgemv).  A separate family: k_gemv_kqt and
-// k_bgemv are not touched; layout, numerics and MFMA operand roles are those of kernels_gemv_kqm.hip (kqm.h is shared by inclusion).
+// k_bgemv are not touched; numerics and MFMA operand roles are those of kernels_gemv_kqm.hip, and the step loads, the unpack and the dot
+// products are the shared ones of kqm.h (layout: t16.h).
 //
 // k_bgemv_kq<QT, B, MODE, NORM, BPW>
 //   split     a workgroup owns 16-row tiles ("units": one tile, or the gate and the up tile of the same rows), its waves split K.  A K
@@ -69,97 +70,6 @@ struct BKqParams {
     uint32_t ring_len;
 };
 
-// one step of a wave on a Q6_K T16 tensor (the loads of q6t_load, kernels_gemv_kqm.hip)
-struct BQ6 { u32x4 qla, qlb, qh, sc; uint32_t d; };
-
-__device__ __forceinline__ BQ6 bq6_load(const uint8_t *base, uint64_t n_tiles, uint32_t NB, uint32_t tile, uint32_t blk, uint32_t lane)
-{
-    const uint64_t tb = (uint64_t)tile * NB + blk;
-    const uint64_t nblk = n_tiles * 16 * NB;
-    BQ6 r;
-    r.qla = load_nt16(base + tb * 3072 + lane * 16);
-    r.qlb = load_nt16(base + tb * 3072 + 1024 + lane * 16);
-    r.qh = load_nt16(base + tb * 3072 + 2048 + lane * 16);
-    r.sc = load_nt16(base + nblk * 192 + tb * 256 + (lane & 15) * 16);
-    r.d = *reinterpret_cast<const GLOBAL_AS uint16_t *>((const GLOBAL_AS uint8_t *)base + nblk * 208 + tb * 32 + (lane & 15) * 2);
-    return r;
-}
-
-// The part of q4t_dot / q6t_dot that does not depend on x, done once per step: the four B operands (one byte per weight) and the scales.
-struct BW4 { i32x4 b[4]; float scv[2], mv[2]; };   // b[2n + hf]: low (n = 0) / high (n = 1) nibbles of q{hf}, the slot order of the A fragments
-struct BW6 { i32x4 b[4]; float sc[4]; float d; };  // b[qd], scales[8n + (G&1) + 2 qd] as floats
-
-__device__ __forceinline__ BW4 bk_unpack(const Q4T &w, uint32_t g)
-{
-    constexpr uint32_t M = 0x0F0F0F0Fu;
-    BW4 u;
-    u.b[0] = __builtin_bit_cast(i32x4, w.q0 & M);
-    u.b[1] = __builtin_bit_cast(i32x4, w.q1 & M);
-    u.b[2] = __builtin_bit_cast(i32x4, (w.q0 >> 4) & M);
-    u.b[3] = __builtin_bit_cast(i32x4, (w.q1 >> 4) & M);
-    // get_scale_min_k4 (ggml) for sub-blocks 2G and 2G+1, branch-free (q4t_dot)
-    const float d = h2f_lo(w.hdr[0]), dmin = h2f_hi(w.hdr[0]);
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const uint32_t sb = 2 * g + h, sh = (sb & 3) * 8;
-        const uint32_t lo8 = (w.hdr[1] >> sh) & 0xFFu, mid = (w.hdr[2] >> sh) & 0xFFu, hi8 = (w.hdr[3] >> sh) & 0xFFu;
-        const bool low = sb < 4;
-        const uint32_t sc = low ? (lo8 & 63u) : ((hi8 & 0xFu) | ((lo8 >> 6) << 4));
-        const uint32_t mn = low ? (mid & 63u) : ((hi8 >> 4) | ((mid >> 6) << 4));
-        u.scv[h] = d * (float)sc;
-        u.mv[h] = dmin * (float)mn;
-    }
-    return u;
-}
-
-__device__ __forceinline__ BW6 bk_unpack(const BQ6 &w, uint32_t g)
-{
-    constexpr uint32_t M4 = 0x0F0F0F0Fu, M2 = 0x30303030u;
-    BW6 u;
-    u.d = h2f_lo(w.d);
-#pragma unroll
-    for (int qd = 0; qd < 4; qd++) {
-        const u32x4 ql = (qd & 1) ? w.qlb : w.qla;
-        const u32x4 lo4 = (qd >= 2) ? ((ql >> 4) & M4) : (ql & M4);
-        const u32x4 hs = qd == 0 ? (w.qh << 4) : (qd == 1 ? (w.qh << 2) : (qd == 2 ? w.qh : (w.qh >> 2)));
-        u.b[qd] = __builtin_bit_cast(i32x4, (hs & M2) | lo4);  // unsigned 6-bit value per byte
-        const uint32_t si = 8 * (g >> 1) + (g & 1) + 2 * qd;
-        const uint32_t sw = si < 8 ? (si < 4 ? w.sc[0] : w.sc[1]) : (si < 12 ? w.sc[2] : w.sc[3]);
-        u.sc[qd] = (float)(int)(int8_t)((sw >> ((si & 3) * 8)) & 0xFFu);
-    }
-    return u;
-}
-
-// 64 weights of one lane against one column: the arithmetic of q4t_dot / q6t_dot (kqm.h, kernels_gemv_kqm.hip) on the unpacked operand
-__device__ __forceinline__ float bk_dot(const BW4 &u, const i32x4 (&af)[4], f32x4 sums)
-{
-    i32x4 dlo = {0, 0, 0, 0}, dhi = {0, 0, 0, 0};
-    dlo = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[0], u.b[0], dlo, 0, 0, 0);
-    dhi = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[2], u.b[2], dhi, 0, 0, 0);
-    dlo = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[1], u.b[1], dlo, 0, 0, 0);
-    dhi = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[3], u.b[3], dhi, 0, 0, 0);
-    // three signed base-256 digits of the fixed-point activations: sum q*x' = S0 + 256*S1 + 65536*S2 (integers, exact)
-    const float vlo = fmaf((float)dlo[2], 65536.0f, fmaf((float)dlo[1], 256.0f, (float)dlo[0]));
-    const float vhi = fmaf((float)dhi[2], 65536.0f, fmaf((float)dhi[1], 256.0f, (float)dhi[0]));
-    float a = u.scv[0] * vlo;
-    a = fmaf(-u.mv[0], sums[0], a);
-    a = fmaf(u.scv[1], vhi, a);
-    a = fmaf(-u.mv[1], sums[1], a);
-    return a;
-}
-
-__device__ __forceinline__ float bk_dot(const BW6 &u, const i32x4 (&af)[4], f32x4 sums)
-{
-    float tot = 0.f;
-#pragma unroll
-    for (int qd = 0; qd < 4; qd++) {
-        const i32x4 dq = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[qd], u.b[qd], i32x4{0, 0, 0, 0}, 0, 0, 0);
-        const float v = fmaf((float)dq[2], 65536.0f, fmaf((float)dq[1], 256.0f, (float)dq[0]));
-        tot = fmaf(u.sc[qd], fmaf(-32.0f, sums[qd], v), tot);
-    }
-    return u.d * tot;
-}
-
 template <int MODE>
 __device__ __forceinline__ void bk_unit(const BKqParams &p, uint32_t u, uint32_t t, uint32_t &seg, uint32_t &tile)
 {
@@ -174,19 +84,13 @@ __device__ __forceinline__ void bk_unit(const BKqParams &p, uint32_t u, uint32_t
     }
 }
 
-__device__ __forceinline__ void bk_kv_store(void *base, int f16, uint64_t idx, float v)
-{
-    if (f16) reinterpret_cast<_Float16 *>(base)[idx] = (_Float16)v;
-    else reinterpret_cast<float *>(base)[idx] = v;
-}
-
 // (at most 8 waves per workgroup and, by its LDS, one workgroup per CU: two waves per SIMD, so a wave may use 256 VGPRs)
 template <int QT, int B, int MODE, bool NORM, int BPW>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_bgemv_kq(const BKqParams p)
 {
     constexpr bool IS6 = QT == NFAI_Q6_K_T16;
     static_assert(IS6 || QT == NFAI_Q4_K_T16, "Q4_K or Q6_K in the T16 layout");
-    using Regs = typename std::conditional<IS6, BQ6, Q4T>::type;
+    using Regs = typename std::conditional<IS6, Q6T, Q4T>::type;
     constexpr int R = MODE == GEMV_GATEUP ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x, lane = tid & 63, nw = blockDim.x >> 6;
@@ -280,7 +184,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             uint32_t seg, tile;
             bk_unit<MODE>(p, blockIdx.x + i_ui * gridDim.x, i_t, seg, tile);
             const uint32_t blk = min(i_tile * NBT + wid * BPW + i_i, p.NB - 1);   // past the end of K: the row's last super-block again (its sum is dropped)
-            if constexpr (IS6) buf = bq6_load(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
+            if constexpr (IS6) buf = q6t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
             else buf = q4t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
             ++ist;
             if (++i_i == (uint32_t)BPW) { i_i = 0; if (++i_t == (uint32_t)R) { i_t = 0; if (++i_ui == nunits) { i_ui = 0; ++i_tile; } } }
@@ -377,7 +281,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     if (lane < 16) {
                         if (role == 0) p.y[b][row] = o;
                         else if (pos_ok[b])   // a position word at or past the capacity writes nothing (the launch reports it through p.err)
-                            bk_kv_store(role == 1 ? p.kc[b] : p.vc[b], p.kv_f16, (uint64_t)posv[b] * p.pos_stride + (uint64_t)head * p.head_stride[b] + dd, o);
+                            kv_store(role == 1 ? p.kc[b] : p.vc[b], p.kv_f16, (uint64_t)posv[b] * p.pos_stride + (uint64_t)head * p.head_stride[b] + dd, o);
                     }
                 }
             }
@@ -399,7 +303,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         const bool live = slot < NBT && c_tile * NBT + slot < p.NB;
         const uint32_t sl_ = min(slot, NBT - 1);
-        const auto uw = bk_unpack(buf, g);
+        const auto uw = kqm_unpack(buf, g);
         // Columns in groups of up to four, without a branch between them (dead columns are multiplied too: their LDS is never
         // written and their sums never read), so that the LDS reads, the MFMAs and the scale epilogues of a group overlap.
         // A fragments: the lanes that carry digits read them, all others read zeros (one address: a broadcast).
@@ -419,7 +323,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
 #pragma unroll
             for (int c = 0; c < CG; c++) {
-                const float a = bk_dot(uw, af[c], sm[c]);
+                const float a = kqm_dot(uw, af[c], sm[c]);
                 acc[I][b0 + c] += live ? ldexpf(a, -sx[c]) : 0.f;  // back from x' = x * 2^S
             }
         }
@@ -631,32 +535,6 @@ hipError_t launch_batch_gemv_kq(const BatchKqArgs &a, hipStream_t s)
     const bool norm = a.gamma != nullptr;
     if (a.w_type == NFAI_Q6_K_T16) return dispatch_bkq_b<NFAI_Q6_K_T16>(p, pl, a.mode, norm, s);
     return dispatch_bkq_b<NFAI_Q4_K_T16>(p, pl, a.mode, norm, s);
-}
-
-// ---- embedding rows of the n tokens from a T16 table, each into its member's own x (k_embed_q4t / k_embed_q6t at n tokens) ----------
-struct BKEmbedParams { const uint8_t *table; int type; uint64_t n_rows; uint32_t E; const uint32_t *tok; float *x[BATCH_MAX]; };
-
-__global__ __launch_bounds__(256) void k_bembed_kq(const BKEmbedParams p)
-{
-    const uint32_t b = blockIdx.y;
-    uint64_t row = p.tok[b];
-    if (row >= p.n_rows) row = p.n_rows - 1;   // (the host checks the tokens it is given; a fed-back ArgMax is always a row)
-    for (uint32_t k = (blockIdx.x * blockDim.x + threadIdx.x) * 4; k < p.E; k += gridDim.x * blockDim.x * 4)
-        *reinterpret_cast<f32x4 *>(p.x[b] + k) = embed_load4(p.table, p.type, p.n_rows, row, k, p.E);
-}
-
-hipError_t launch_batch_embed_kq(const void *table, int type, uint64_t n_rows, uint32_t E, const uint32_t *tok, float *const *x, uint32_t n, hipStream_t s)
-{
-    if (!table || !tok || n < 1 || n > BATCH_MAX || E % 256 || n_rows == 0 || n_rows % 16) return hipErrorInvalidValue;
-    if (type != NFAI_Q4_K_T16 && type != NFAI_Q6_K_T16) return hipErrorInvalidValue;
-    BKEmbedParams p{};
-    p.table = static_cast<const uint8_t *>(table); p.type = type; p.n_rows = n_rows; p.E = E; p.tok = tok;
-    for (uint32_t b = 0; b < n; b++) {
-        if (!x[b]) return hipErrorInvalidValue;
-        p.x[b] = x[b];
-    }
-    hipLaunchKernelGGL(k_bembed_kq, dim3((E / 4 + 255) / 256, n), dim3(256), 0, s, p);
-    return hipGetLastError();
 }
 
 }  // namespace nfai

@@ -197,12 +197,6 @@ __device__ __forceinline__ float q6_dot(const Q6Regs &r, const float *xs, uint32
     return fmaf(d, tot, acc);
 }
 
-__device__ __forceinline__ void kq_kv_store(void *base, int f16, uint64_t idx, float v)
-{
-    if (f16) reinterpret_cast<_Float16 *>(base)[idx] = (_Float16)v;
-    else reinterpret_cast<float *>(base)[idx] = v;
-}
-
 template <int MODE>
 __device__ __forceinline__ void kq_epilogue(const KqParams &p, uint32_t unit, float a0, float a1)
 {
@@ -229,8 +223,8 @@ __device__ __forceinline__ void kq_epilogue(const KqParams &p, uint32_t unit, fl
         } else {
             const uint64_t idx = (uint64_t)p.pos[0] * p.kv_pos_stride + (uint64_t)head * p.kv_head_stride + d;
             void *base = seg == 1 ? p.kc : p.vc;
-            kq_kv_store(base, p.kv_f16, idx, o0);
-            kq_kv_store(base, p.kv_f16, idx + 1, o1);
+            kv_store(base, p.kv_f16, idx, o0);
+            kv_store(base, p.kv_f16, idx + 1, o1);
         }
     }
 }
@@ -418,8 +412,7 @@ __global__ void k_embed_kq(const uint8_t *table, uint64_t n_rows, const uint32_t
         const uint8_t *scales = b + 4;
         const uint32_t sb = kk >> 5, l = kk & 31;
         uint32_t sc, m;
-        if (sb < 4) { sc = scales[sb] & 63; m = scales[sb + 4] & 63; }
-        else { sc = (scales[sb + 4] & 0xF) | ((scales[sb - 4] >> 6) << 4); m = (scales[sb + 4] >> 4) | ((scales[sb] >> 6) << 4); }
+        k4_scale_min_bytes(scales, sb, sc, m);
         const uint8_t q = b[16 + (sb >> 1) * 32 + l];
         const float qv = (float)((sb & 1) ? (q >> 4) : (q & 0xF));
         y[k] = d * (float)sc * qv - dmin * (float)m;

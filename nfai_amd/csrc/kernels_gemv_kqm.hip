@@ -21,19 +21,7 @@
 // the largest |x| of the super-block.  Against the fp32 oracle the differences are at the level of
 // fp32 summation-order noise (tests/test_gpu_kquant.py states the tolerance; max |dlogit| 1.5e-5 at 3B).
 //
-// HBM layout ("T16", repacked once at upload, same bytes): rows are grouped in tiles of 16.
-//   Q4_K: plane 0  [tile][blk][h:2][lane:64][16 B]  lane = G*16 + r holds qs[32G+16h .. +16) of row 16*tile+r,
-//                  i.e. lane group G owns sub-blocks 2G (low nibbles) and 2G+1 (high nibbles) of its row;
-//         plane 1  [tile][blk][r:16][16 B]          d, dmin, 12 scale bytes of row 16*tile+r.
-//   Q5_K: planes 0 and 1 of Q4_K (same bytes: qs and the 16-byte header), and
-//         plane 2  [tile][blk][lane:64][8 B]        the 64 fifth bits (qh) of the weights lane (G, r) unpacks, in the order of
-//                                                   q5t_dot (kqm.h): one shift and one v_and_or_b32 per four weights.
-//   Q6_K: see k_repack_q6k_t16.
-//   Q8_0: plane 0  [tile][blk][h:4][lane:64][16 B]  lane = G*16 + r holds qs bytes 64h + 16G .. +16 of super-block blk of
-//                  row 16*tile+r: 16 weights of ONE 32-block (2h + (G >> 1)), so one d per lane and MFMA;
-//         plane 1  [tile][blk][r:16][16 B]          the eight fp16 d of that row and super-block, d of 32-block b at half
-//                                                   (b & 1) * 4 + (b >> 1): lanes of group G read the 8 bytes of their four d.
-// Every wave-wide load is one contiguous kilobyte (quants), 512 bytes (Q5_K high bits) or 256 bytes (headers).
+// HBM layout: "T16", repacked once at upload, same bytes: t16.h.  Lane (G, r) of a wave owns 64 weights of row r of a 16-row tile.
 //
 // Work split: a workgroup owns whole 16-row tiles ("units": one tile, or the gate and the up tile of
 // the same rows); its waves split K (wave w owns super-blocks w*BPW .. w*BPW+BPW-1 of every tile and
@@ -66,53 +54,6 @@ __device__ __forceinline__ void kqm_unit(const KqmParams &p, uint32_t u, int t, 
     } else {
         seg = 0; tile = u;
     }
-}
-
-struct Q6T { u32x4 qla, qlb, qh, sc; uint32_t d; };
-
-__device__ __forceinline__ Q6T q6t_load(const KqmParams &p, uint32_t seg, uint32_t tile, uint32_t blk, uint32_t lane)
-{
-    const uint64_t tb = (uint64_t)tile * p.NB + blk;
-    const uint64_t nblk = (uint64_t)p.seg_tiles[seg] * 16 * p.NB;
-    const uint8_t *base = p.W[seg];
-    Q6T r;
-    r.qla = load_nt16(base + tb * 3072 + lane * 16);
-    r.qlb = load_nt16(base + tb * 3072 + 1024 + lane * 16);
-    r.qh = load_nt16(base + tb * 3072 + 2048 + lane * 16);
-    r.sc = load_nt16(base + nblk * 192 + tb * 256 + (lane & 15) * 16);
-    r.d = *reinterpret_cast<const GLOBAL_AS uint16_t *>((const GLOBAL_AS uint8_t *)base + nblk * 208 + tb * 32 + (lane & 15) * 2);
-    return r;
-}
-
-// 64 weights of one lane: half n = G>>1 of the super-block, columns l = 16*(G&1) .. +15 of all four quarters
-// (ggml dequantize_row_q6_K: quarter 0/2 = low/high nibbles of ql[l], quarter 1/3 = of ql[l+32], bits 2q..2q+1 of qh[l]);
-// one MFMA per quarter = one 16-weight scale group.  sums = sum of x' over each of the four groups.
-__device__ __forceinline__ float q6t_dot(const Q6T &w, const i32x4 (&af)[4], f32x4 sums, uint32_t g)
-{
-    constexpr uint32_t M4 = 0x0F0F0F0Fu, M2 = 0x30303030u;
-    const float d = h2f_lo(w.d);
-    float tot = 0.f;
-#pragma unroll
-    for (int qd = 0; qd < 4; qd++) {
-        const u32x4 ql = (qd & 1) ? w.qlb : w.qla;
-        const u32x4 lo4 = (qd >= 2) ? ((ql >> 4) & M4) : (ql & M4);
-        const u32x4 hs = qd == 0 ? (w.qh << 4) : (qd == 1 ? (w.qh << 2) : (qd == 2 ? w.qh : (w.qh >> 2)));
-        const u32x4 b = (hs & M2) | lo4;  // unsigned 6-bit value per byte
-        const i32x4 dq = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[qd], __builtin_bit_cast(i32x4, b), i32x4{0, 0, 0, 0}, 0, 0, 0);
-        const float v = fmaf((float)dq[2], 65536.0f, fmaf((float)dq[1], 256.0f, (float)dq[0]));
-        // scales[8n + (G&1) + 2*qd] of the row
-        const uint32_t si = 8 * (g >> 1) + (g & 1) + 2 * qd;
-        const uint32_t sw = si < 8 ? (si < 4 ? w.sc[0] : w.sc[1]) : (si < 12 ? w.sc[2] : w.sc[3]);
-        const int sc = (int)(int8_t)((sw >> ((si & 3) * 8)) & 0xFFu);
-        tot = fmaf((float)sc, fmaf(-32.0f, sums[qd], v), tot);
-    }
-    return d * tot;
-}
-
-__device__ __forceinline__ void kqm_kv_store(void *base, int f16, uint64_t idx, float v)
-{
-    if (f16) reinterpret_cast<_Float16 *>(base)[idx] = (_Float16)v;
-    else reinterpret_cast<float *>(base)[idx] = v;
 }
 
 // What the epilogue of unit u reads besides the dot products; loaded unconditionally (clamped) so that the
@@ -166,7 +107,7 @@ __device__ __forceinline__ void kqm_epilogue(const KqmParams &p, uint32_t u, uin
         }
         if (lane < 16) {
             if (seg == 0) p.y[row] = o;
-            else kqm_kv_store(seg == 1 ? p.kc : p.vc, p.kv_f16, (uint64_t)pre.pos * p.kv_pos_stride + (uint64_t)head * p.kv_head_stride + dd, o);
+            else kv_store(seg == 1 ? p.kc : p.vc, p.kv_f16, (uint64_t)pre.pos * p.kv_pos_stride + (uint64_t)head * p.kv_head_stride + dd, o);
         }
     }
 }
@@ -459,114 +400,89 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
     }
 }
 
-// ---- Q4_K repack: native 144-byte blocks (row-major) -> T16 planes (same bytes) ------------------------
+// ---- repack: native ggml blocks (row-major) -> T16 planes (same bytes), one workgroup per (tile, super-block) -----------------------
+template <class Kern>
+static hipError_t launch_repack_t16(Kern kern, uint32_t block, const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
+{
+    if (rows == 0) return hipSuccess;
+    if (rows % 16 || cols % 256) return hipErrorInvalidValue;
+    const uint64_t nb = cols / 256, grid = rows / 16 * nb;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    kern<<<(uint32_t)grid, block, 0, s>>>(static_cast<const uint8_t *>(native), static_cast<uint8_t *>(tiled), (uint32_t)(rows / 16), (uint32_t)nb);
+    return hipGetLastError();
+}
+
+// ---- Q4_K repack: native 144-byte blocks (row-major: d, dmin, scales[12], qs[128]) -> T16 planes (same bytes) ---------------------
 __global__ void k_repack_q4k_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
 {
     const uint64_t tb = blockIdx.x;  // tile * NB + blk
     const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB), t = threadIdx.x;
-    const uint64_t nblk = (uint64_t)n_tiles * 16 * NB;
+    const uint64_t nblk = t16_nblk(n_tiles, NB);
     if (t < 128) {
         const uint32_t h = t >> 6, ln = t & 63, G = ln >> 4, r = ln & 15;
-        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB + blk) * 144 + 16 + 32 * G + 16 * h;
-        *reinterpret_cast<u32x4 *>(dst + tb * 2048 + h * 1024 + ln * 16) = *reinterpret_cast<const u32x4 *>(s);
+        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB + blk) * GGML_Q4_K_BLOCK + 16 + 32 * G + 16 * h;
+        *reinterpret_cast<u32x4 *>(t16_k4_qs(dst, tb) + h * 1024 + ln * 16) = *reinterpret_cast<const u32x4 *>(s);
     } else if (t < 144) {
         const uint32_t r = t - 128;
-        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB + blk) * 144;
-        *reinterpret_cast<u32x4 *>(dst + nblk * 128 + tb * 256 + r * 16) = *reinterpret_cast<const u32x4 *>(s);
+        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB + blk) * GGML_Q4_K_BLOCK;
+        *reinterpret_cast<u32x4 *>(t16_k4_hdr(dst, nblk, tb) + r * 16) = *reinterpret_cast<const u32x4 *>(s);
     }
 }
 
-hipError_t launch_repack_q4k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
-{
-    if (rows == 0) return hipSuccess;
-    if (rows % 16 || cols % 256) return hipErrorInvalidValue;
-    const uint64_t nb = cols / 256, grid = rows / 16 * nb;
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    k_repack_q4k_t16<<<(uint32_t)grid, 192, 0, s>>>(static_cast<const uint8_t *>(native), static_cast<uint8_t *>(tiled), (uint32_t)(rows / 16),
-                                                    (uint32_t)nb);
-    return hipGetLastError();
-}
-
-// ---- Q6_K repack: native 210-byte blocks (row-major) -> T16 planes (same bytes) ------------------------
-//   plane 0  [tile][blk][piece:3][lane:64][16 B]  lane = G*16 + r, n = G>>1, lh = G&1:
-//            piece 0 = ql[64n + 16lh ..+16), piece 1 = ql[64n + 32 + 16lh ..+16), piece 2 = qh[32n + 16lh ..+16)
-//   plane 1  [tile][blk][r:16][16 B]  the 16 int8 scales      plane 2  [tile][blk][r:16] fp16 d
+// ---- Q6_K repack: native 210-byte blocks (row-major: ql[128], qh[64], scales[16], d) -> T16 planes (same bytes) -----------------
 __global__ void k_repack_q6k_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
 {
     const uint64_t tb = blockIdx.x;
     const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB), t = threadIdx.x;
-    const uint64_t nblk = (uint64_t)n_tiles * 16 * NB;
+    const uint64_t nblk = t16_nblk(n_tiles, NB);
     // native blocks are only 2-byte aligned: byte copies
     for (uint32_t e = t; e < 3072; e += blockDim.x) {
         const uint32_t piece = e >> 10, ln = (e >> 4) & 63, b = e & 15, G = ln >> 4, r = ln & 15, n = G >> 1, lh = G & 1;
-        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB + blk) * 210;
+        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB + blk) * GGML_Q6_K_BLOCK;
         const uint32_t off = piece == 0 ? 64 * n + 16 * lh : (piece == 1 ? 64 * n + 32 + 16 * lh : 128 + 32 * n + 16 * lh);
-        dst[tb * 3072 + e] = s[off + b];
+        t16_q6k_q(dst, tb)[e] = s[off + b];
     }
     for (uint32_t e = t; e < 256; e += blockDim.x) {
         const uint32_t r = e >> 4, b = e & 15;
-        dst[nblk * 192 + tb * 256 + e] = src[((uint64_t)(tile * 16 + r) * NB + blk) * 210 + 192 + b];
+        t16_q6k_sc(dst, nblk, tb)[e] = src[((uint64_t)(tile * 16 + r) * NB + blk) * GGML_Q6_K_BLOCK + 192 + b];
     }
-    if (t < 32) dst[nblk * 208 + tb * 32 + t] = src[((uint64_t)(tile * 16 + (t >> 1)) * NB + blk) * 210 + 208 + (t & 1)];
+    if (t < 32) t16_q6k_d(dst, nblk, tb)[t] = src[((uint64_t)(tile * 16 + (t >> 1)) * NB + blk) * GGML_Q6_K_BLOCK + 208 + (t & 1)];
 }
 
-hipError_t launch_repack_q6k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
-{
-    if (rows == 0) return hipSuccess;
-    if (rows % 16 || cols % 256) return hipErrorInvalidValue;
-    const uint64_t nb = cols / 256, grid = rows / 16 * nb;
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    k_repack_q6k_t16<<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(native), static_cast<uint8_t *>(tiled), (uint32_t)(rows / 16),
-                                                    (uint32_t)nb);
-    return hipGetLastError();
-}
-
-// ---- Q8_0 repack: native 34-byte blocks (row-major) -> T16 planes (same bytes; layout in the header comment) ------------
+// ---- Q8_0 repack: native 34-byte blocks (row-major: d, qs[32]) -> T16 planes (same bytes) ---------------------------------
 __global__ void k_repack_q80_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
 {
     const uint64_t tb = blockIdx.x;
     const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB), t = threadIdx.x;
-    const uint64_t nblk = (uint64_t)n_tiles * 16 * NB;
+    const uint64_t nblk = t16_nblk(n_tiles, NB);
     // native blocks are only 2-byte aligned: byte copies
     for (uint32_t e = t; e < 4096; e += blockDim.x) {
         const uint32_t h = e >> 10, ln = (e >> 4) & 63, b = e & 15, G = ln >> 4, r = ln & 15, kk = 64 * h + 16 * G + b;
-        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB * 8 + blk * 8 + (kk >> 5)) * 34;
-        dst[tb * 4096 + e] = s[2 + (kk & 31)];
+        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB * 8 + blk * 8 + (kk >> 5)) * GGML_Q8_0_BLOCK;
+        t16_q80_qs(dst, tb)[e] = s[2 + (kk & 31)];
     }
     for (uint32_t e = t; e < 256; e += blockDim.x) {
         const uint32_t r = e >> 4, i = (e & 15) >> 1, b32 = 2 * (i & 3) + (i >> 2);  // half i of the row = d of 32-block b32
-        dst[nblk * 256 + tb * 256 + e] = src[((uint64_t)(tile * 16 + r) * NB * 8 + blk * 8 + b32) * 34 + (e & 1)];
+        t16_q80_d(dst, nblk, tb)[e] = src[((uint64_t)(tile * 16 + r) * NB * 8 + blk * 8 + b32) * GGML_Q8_0_BLOCK + (e & 1)];
     }
 }
 
-hipError_t launch_repack_q80_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
-{
-    if (rows == 0) return hipSuccess;
-    if (rows % 16 || cols % 256) return hipErrorInvalidValue;
-    const uint64_t nb = cols / 256, grid = rows / 16 * nb;
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    k_repack_q80_t16<<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(native), static_cast<uint8_t *>(tiled), (uint32_t)(rows / 16),
-                                                    (uint32_t)nb);
-    return hipGetLastError();
-}
-
 // ---- Q5_K repack: native 176-byte blocks (row-major: d, dmin, scales[12], qh[32], qs[128]) -> T16 planes -------------------
-// Planes 0 and 1 as k_repack_q4k_t16 (qs at byte 48 of the block, the header is its first 16 bytes).  Plane 2: word hf of lane
-// (G, r) holds, for the weights l = 16hf + 4i + b (b = byte of dword i of q{hf}), bit 2G of qh[l] at 8b + i and bit 2G+1 at 8b + 4 + i.
+// Planes 0 and 1 as k_repack_q4k_t16 (qs at byte 48 of the block, the header is its first 16 bytes); plane 2: the bit order of t16.h.
 __global__ void k_repack_q5k_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
 {
     const uint64_t tb = blockIdx.x;
     const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB), t = threadIdx.x;
-    const uint64_t nblk = (uint64_t)n_tiles * 16 * NB;
+    const uint64_t nblk = t16_nblk(n_tiles, NB);
     if (t < 128) {
         const uint32_t h = t >> 6, ln = t & 63, G = ln >> 4, r = ln & 15;
-        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB + blk) * 176 + 48 + 32 * G + 16 * h;
-        *reinterpret_cast<u32x4 *>(dst + tb * 2048 + h * 1024 + ln * 16) = *reinterpret_cast<const u32x4 *>(s);
+        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB + blk) * GGML_Q5_K_BLOCK + 48 + 32 * G + 16 * h;
+        *reinterpret_cast<u32x4 *>(t16_k4_qs(dst, tb) + h * 1024 + ln * 16) = *reinterpret_cast<const u32x4 *>(s);
     } else if (t < 256) {
         const uint32_t hf = t & 1, ln = (t - 128) >> 1, G = ln >> 4, r = ln & 15;
-        const uint8_t *blkp = src + ((uint64_t)(tile * 16 + r) * NB + blk) * 176;
-        if (t < 144) *reinterpret_cast<u32x4 *>(dst + nblk * 128 + tb * 256 + (t - 128) * 16) =
-            *reinterpret_cast<const u32x4 *>(src + ((uint64_t)(tile * 16 + (t - 128)) * NB + blk) * 176);
+        const uint8_t *blkp = src + ((uint64_t)(tile * 16 + r) * NB + blk) * GGML_Q5_K_BLOCK;
+        if (t < 144) *reinterpret_cast<u32x4 *>(t16_k4_hdr(dst, nblk, tb) + (t - 128) * 16) =
+            *reinterpret_cast<const u32x4 *>(src + ((uint64_t)(tile * 16 + (t - 128)) * NB + blk) * GGML_Q5_K_BLOCK);
         const u32x4 qh = *reinterpret_cast<const u32x4 *>(blkp + 16 + 16 * hf);  // qh[16hf .. 16hf + 16)
         uint32_t word = 0;
 #pragma unroll
@@ -575,110 +491,67 @@ __global__ void k_repack_q5k_t16(const uint8_t *src, uint8_t *dst, uint32_t n_ti
             word |= ((byte >> (2 * G)) & 1u) << (8 * b + i);
             word |= ((byte >> (2 * G + 1)) & 1u) << (8 * b + 4 + i);
         }
-        *reinterpret_cast<uint32_t *>(dst + nblk * 144 + tb * 512 + ln * 8 + hf * 4) = word;
+        *reinterpret_cast<uint32_t *>(t16_q5k_qh(dst, nblk, tb) + ln * 8 + hf * 4) = word;
     }
 }
 
+hipError_t launch_repack_q4k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
+{
+    return launch_repack_t16(k_repack_q4k_t16, 192, native, tiled, rows, cols, s);
+}
+hipError_t launch_repack_q6k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
+{
+    return launch_repack_t16(k_repack_q6k_t16, 256, native, tiled, rows, cols, s);
+}
+hipError_t launch_repack_q80_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
+{
+    return launch_repack_t16(k_repack_q80_t16, 256, native, tiled, rows, cols, s);
+}
 hipError_t launch_repack_q5k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
 {
-    if (rows == 0) return hipSuccess;
-    if (rows % 16 || cols % 256) return hipErrorInvalidValue;
-    const uint64_t nb = cols / 256, grid = rows / 16 * nb;
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    k_repack_q5k_t16<<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(native), static_cast<uint8_t *>(tiled), (uint32_t)(rows / 16),
-                                                    (uint32_t)nb);
-    return hipGetLastError();
+    return launch_repack_t16(k_repack_q5k_t16, 256, native, tiled, rows, cols, s);
 }
 
-__global__ void k_embed_q5t(const uint8_t *table, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= E) return;
-    tok += blockIdx.y;
-    y += (uint64_t)blockIdx.y * E;
-    const uint32_t NB = E / 256, blk = k >> 8, kk = k & 255, sb = kk >> 5, l = kk & 31;
-    const uint64_t row = tok[0], tile = row >> 4, r = row & 15, tb = tile * NB + blk, nblk = n_rows * NB;
-    const uint8_t *hdr = table + nblk * 128 + tb * 256 + r * 16;
-    const float d = (float)*reinterpret_cast<const _Float16 *>(hdr), dmin = (float)*reinterpret_cast<const _Float16 *>(hdr + 2);
-    const uint8_t *scales = hdr + 4;
-    uint32_t sc, m;
-    if (sb < 4) { sc = scales[sb] & 63; m = scales[sb + 4] & 63; }
-    else { sc = (scales[sb + 4] & 0xF) | ((scales[sb - 4] >> 6) << 4); m = (scales[sb + 4] >> 4) | ((scales[sb] >> 6) << 4); }
-    const uint32_t ln = (sb >> 1) * 16 + (uint32_t)r;
-    const uint8_t q = table[tb * 2048 + (l >> 4) * 1024 + ln * 16 + (l & 15)];
-    const uint32_t hw = *reinterpret_cast<const uint32_t *>(table + nblk * 144 + tb * 512 + ln * 8 + (l >> 4) * 4);
-    const uint32_t bit = (hw >> (8 * (l & 3) + 4 * (sb & 1) + ((l >> 2) & 3))) & 1u;
-    const float qv = (float)(((sb & 1) ? (q >> 4) : (q & 0xF)) | (bit << 4));
-    y[k] = d * (float)sc * qv - dmin * (float)m;
-}
+// ---- rows of a T16 table -> fp32 (embedding gather): row tok[t] to y + t * E (prefill, single token) or, y == nullptr, to x[t] (the
+// members of a decode batch), four elements per thread -------------------------------------------------------------------------------
+struct EmbedT16Params { const uint8_t *table; int type; uint64_t n_rows; uint32_t E; const uint32_t *tok; float *y; float *x[BATCH_MAX]; };
 
-__global__ void k_embed_q8t(const uint8_t *table, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E)
+__global__ __launch_bounds__(256) void k_embed_t16(const EmbedT16Params p)
 {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= E) return;
-    tok += blockIdx.y;
-    y += (uint64_t)blockIdx.y * E;
-    const uint32_t NB = E / 256, blk = k >> 8, kk = k & 255;
-    const uint64_t row = tok[0], tile = row >> 4, r = row & 15, tb = tile * NB + blk, nblk = n_rows * NB;
-    const uint32_t ln = ((kk >> 4) & 3) * 16 + (uint32_t)r;
-    const int8_t q = (int8_t)table[tb * 4096 + (kk >> 6) * 1024 + ln * 16 + (kk & 15)];
-    const uint32_t b32 = kk >> 5;
-    const float d = (float)reinterpret_cast<const _Float16 *>(table + nblk * 256 + tb * 256 + r * 16)[(b32 & 1) * 4 + (b32 >> 1)];
-    y[k] = d * (float)q;
-}
-
-__global__ void k_embed_q6t(const uint8_t *table, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= E) return;
-    tok += blockIdx.y;
-    y += (uint64_t)blockIdx.y * E;
-    const uint32_t NB = E / 256, blk = k >> 8, kk = k & 255, n = kk >> 7, qd = (kk >> 5) & 3, l = kk & 31, lh = l >> 4, b = l & 15;
-    const uint64_t row = tok[0], tile = row >> 4, r = row & 15, tb = tile * NB + blk, nblk = n_rows * NB;
-    const uint32_t ln = (n * 2 + lh) * 16 + (uint32_t)r;
-    const uint8_t ql = table[tb * 3072 + (qd & 1) * 1024 + ln * 16 + b];
-    const uint8_t qh = table[tb * 3072 + 2048 + ln * 16 + b];
-    const int8_t sc = (int8_t)table[nblk * 192 + tb * 256 + r * 16 + 8 * n + lh + 2 * qd];
-    const float d = (float)reinterpret_cast<const _Float16 *>(table + nblk * 208 + tb * 32)[r];
-    const int q = (int)(((qd >= 2) ? (ql >> 4) : (ql & 0xF)) | (((qh >> (2 * qd)) & 3) << 4)) - 32;
-    y[k] = d * (float)sc * (float)q;
-}
-
-// ---- one row of a T16 table -> fp32 (embedding gather) ----------------------------------------------------
-__global__ void k_embed_q4t(const uint8_t *table, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= E) return;
-    tok += blockIdx.y;  // row t of a batch (prefill) -> y[t][E]
-    y += (uint64_t)blockIdx.y * E;
-    const uint32_t NB = E / 256, blk = k >> 8, kk = k & 255, sb = kk >> 5, l = kk & 31;
-    const uint64_t row = tok[0], tile = row >> 4, r = row & 15, tb = tile * NB + blk, nblk = n_rows * NB;
-    const uint8_t *hdr = table + nblk * 128 + tb * 256 + r * 16;
-    const float d = (float)*reinterpret_cast<const _Float16 *>(hdr), dmin = (float)*reinterpret_cast<const _Float16 *>(hdr + 2);
-    const uint8_t *scales = hdr + 4;
-    uint32_t sc, m;
-    if (sb < 4) { sc = scales[sb] & 63; m = scales[sb + 4] & 63; }
-    else { sc = (scales[sb + 4] & 0xF) | ((scales[sb - 4] >> 6) << 4); m = (scales[sb + 4] >> 4) | ((scales[sb] >> 6) << 4); }
-    const uint8_t q = table[tb * 2048 + (l >> 4) * 1024 + ((sb >> 1) * 16 + r) * 16 + (l & 15)];
-    const float qv = (float)((sb & 1) ? (q >> 4) : (q & 0xF));
-    y[k] = d * (float)sc * qv - dmin * (float)m;
+    const uint32_t t = blockIdx.y;
+    uint64_t row = p.tok[t];
+    if (row >= p.n_rows) row = p.n_rows - 1;   // (the host checks the tokens it is given; a fed-back ArgMax is always a row)
+    float *out = p.y ? p.y + (uint64_t)t * p.E : p.x[t];
+    for (uint32_t k = (blockIdx.x * blockDim.x + threadIdx.x) * 4; k < p.E; k += gridDim.x * blockDim.x * 4)
+        *reinterpret_cast<f32x4 *>(out + k) = t16_row_load4(p.table, p.type, p.n_rows, row, k, p.E);
 }
 
 hipError_t launch_embed_rows_kqt(const void *table, int type, uint64_t n_rows, const uint32_t *toks, float *y, uint32_t T, uint32_t E, hipStream_t s)
 {
-    if (E % 256 || n_rows % 16 || T == 0) return hipErrorInvalidValue;
-    const dim3 grid((E + 255) / 256, T);
-    if (type == NFAI_Q4_K_T16) k_embed_q4t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
-    else if (type == NFAI_Q6_K_T16) k_embed_q6t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
-    else if (type == NFAI_Q8_0_T16) k_embed_q8t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
-    else if (type == NFAI_Q5_K_T16) k_embed_q5t<<<grid, 256, 0, s>>>(static_cast<const uint8_t *>(table), n_rows, toks, y, E);
-    else return hipErrorInvalidValue;
+    if (E % 256 || n_rows == 0 || n_rows % 16 || T == 0 || !y || !is_t16(type)) return hipErrorInvalidValue;
+    EmbedT16Params p{};
+    p.table = static_cast<const uint8_t *>(table); p.type = type; p.n_rows = n_rows; p.E = E; p.tok = toks; p.y = y;
+    hipLaunchKernelGGL(k_embed_t16, dim3((E / 4 + 255) / 256, T), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_embed_kqt(const void *table, int type, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E, hipStream_t s)
 {
     return launch_embed_rows_kqt(table, type, n_rows, tok, y, 1, E, s);
+}
+
+hipError_t launch_batch_embed_kq(const void *table, int type, uint64_t n_rows, uint32_t E, const uint32_t *tok, float *const *x, uint32_t n, hipStream_t s)
+{
+    if (!table || !tok || n < 1 || n > BATCH_MAX || E % 256 || n_rows == 0 || n_rows % 16) return hipErrorInvalidValue;
+    if (type != NFAI_Q4_K_T16 && type != NFAI_Q6_K_T16) return hipErrorInvalidValue;
+    EmbedT16Params p{};
+    p.table = static_cast<const uint8_t *>(table); p.type = type; p.n_rows = n_rows; p.E = E; p.tok = tok;
+    for (uint32_t b = 0; b < n; b++) {
+        if (!x[b]) return hipErrorInvalidValue;
+        p.x[b] = x[b];
+    }
+    hipLaunchKernelGGL(k_embed_t16, dim3((E / 4 + 255) / 256, n), dim3(256), 0, s, p);
+    return hipGetLastError();
 }
 
 // ---- T16 tensor -> fp16 [rows][cols] (K-quant prefill: one block's matrices are widened into a scratch buffer and
@@ -703,21 +576,19 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
     if (tb >= (uint64_t)n_tiles * NB) return;
     const uint32_t lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
     const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB);
-    const uint64_t nblk = (uint64_t)n_tiles * 16 * NB;
+    const uint64_t nblk = t16_nblk(n_tiles, NB);
     _Float16 *orow = reinterpret_cast<_Float16 *>(stage[threadIdx.x >> 6] + r * DQ_ROW);
     if constexpr (QT == NFAI_Q4_K_T16 || QT == NFAI_Q5_K_T16) {
-        const u32x4 q0 = load_nt16(W + tb * 2048 + lane * 16), q1 = load_nt16(W + tb * 2048 + 1024 + lane * 16);
-        const u32x4 hdr = load_nt16(W + nblk * 128 + tb * 256 + r * 16);
+        const u32x4 q0 = load_nt16(t16_k4_qs(W, tb) + lane * 16), q1 = load_nt16(t16_k4_qs(W, tb) + 1024 + lane * 16);
+        const u32x4 hdr = load_nt16(t16_k4_hdr(W, nblk, tb) + r * 16);
         u32x2 qh5 = {0u, 0u};  // Q5_K: the high-bit plane (bit order of q5t_dot)
-        if constexpr (QT == NFAI_Q5_K_T16) qh5 = *reinterpret_cast<const u32x2 *>(W + nblk * 144 + tb * 512 + lane * 8);
+        if constexpr (QT == NFAI_Q5_K_T16) qh5 = *reinterpret_cast<const u32x2 *>(t16_q5k_qh(W, nblk, tb) + lane * 8);
         const float d = h2f_lo(hdr[0]), dmin = h2f_hi(hdr[0]);
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-            const uint32_t sb = 2 * g + h, sh = (sb & 3) * 8;
-            const uint32_t lo8 = (hdr[1] >> sh) & 0xFFu, mid = (hdr[2] >> sh) & 0xFFu, hi8 = (hdr[3] >> sh) & 0xFFu;
-            const bool low = sb < 4;
-            const uint32_t sc = low ? (lo8 & 63u) : ((hi8 & 0xFu) | ((lo8 >> 6) << 4));
-            const uint32_t mn = low ? (mid & 63u) : ((hi8 >> 4) | ((mid >> 6) << 4));
+            const uint32_t sb = 2 * g + h;
+            uint32_t sc, mn;
+            k4_scale_min(hdr, sb, sc, mn);
             const float d1 = d * (float)sc, m1 = dmin * (float)mn;
 #pragma unroll
             for (int c = 0; c < 4; c++) {  // 8 weights = bytes 8c .. 8c+7 of the 32-byte run
@@ -736,10 +607,10 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
             }
         }
     } else if constexpr (QT == NFAI_Q8_0_T16) {
-        const u32x4 dv = load_nt16(W + nblk * 256 + tb * 256 + r * 16);
+        const u32x4 dv = load_nt16(t16_q80_d(W, nblk, tb) + r * 16);
 #pragma unroll
         for (int h = 0; h < 4; h++) {  // weights 64h + 16g .. +16 of row r: 32-block 2h + (g >> 1), its d at half (g >> 1) * 4 + h
-            const u32x4 q = load_nt16(W + tb * 4096 + h * 1024 + lane * 16);
+            const u32x4 q = load_nt16(t16_q80_qs(W, tb) + h * 1024 + lane * 16);
             const uint32_t dw = (g >> 1) ? dv[2 + (h >> 1)] : dv[h >> 1];
             const float d = (h & 1) ? h2f_hi(dw) : h2f_lo(dw);
 #pragma unroll
@@ -751,17 +622,15 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
             }
         }
     } else {
-        const u32x4 qla = load_nt16(W + tb * 3072 + lane * 16), qlb = load_nt16(W + tb * 3072 + 1024 + lane * 16);
-        const u32x4 qh = load_nt16(W + tb * 3072 + 2048 + lane * 16);
-        const u32x4 scv = load_nt16(W + nblk * 192 + tb * 256 + r * 16);
-        const float d = (float)*reinterpret_cast<const _Float16 *>(W + nblk * 208 + tb * 32 + r * 2);
+        const u32x4 qla = load_nt16(t16_q6k_q(W, tb) + lane * 16), qlb = load_nt16(t16_q6k_q(W, tb) + 1024 + lane * 16);
+        const u32x4 qh = load_nt16(t16_q6k_q(W, tb) + 2048 + lane * 16);
+        const u32x4 scv = load_nt16(t16_q6k_sc(W, nblk, tb) + r * 16);
+        const float d = (float)*reinterpret_cast<const _Float16 *>(t16_q6k_d(W, nblk, tb) + r * 2);
         const uint32_t n = g >> 1, lh = g & 1;
 #pragma unroll
         for (int qd = 0; qd < 4; qd++) {
             const u32x4 ql = (qd & 1) ? qlb : qla;
-            const uint32_t si = 8 * n + lh + 2 * qd;
-            const uint32_t sw = si < 8 ? (si < 4 ? scv[0] : scv[1]) : (si < 12 ? scv[2] : scv[3]);
-            const float dsc = d * (float)(int)(int8_t)((sw >> ((si & 3) * 8)) & 0xFFu);
+            const float dsc = d * (float)q6k_scale(scv, 8 * n + lh + 2 * qd);
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 f16x8 o;
@@ -855,6 +724,18 @@ static hipError_t q4t_bpw(const KqmParams &p, int bpw, uint32_t grid, uint32_t b
     return q4t_launch<QT, MODE, 8>(p, ns, grid, block, lds, s);
 }
 
+template <int QT>
+static hipError_t q4t_mode(const KqmParams &p, int mode, int bpw, uint32_t grid, uint32_t block, size_t lds, hipStream_t s)
+{
+    switch (mode) {
+        case GEMV_PLAIN: return q4t_bpw<QT, GEMV_PLAIN>(p, bpw, grid, block, lds, s);
+        case GEMV_RESIDUAL: return q4t_bpw<QT, GEMV_RESIDUAL>(p, bpw, grid, block, lds, s);
+        case GEMV_QKV_ROPE: return q4t_bpw<QT, GEMV_QKV_ROPE>(p, bpw, grid, block, lds, s);
+        case GEMV_GATEUP: return q4t_bpw<QT, GEMV_GATEUP>(p, bpw, grid, block, lds, s);
+    }
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s)
 {
     if (!is_t16(a.w_type) && a.w_type != NFAI_KQ_MIXED && a.w_type != NFAI_KQ_MIXED5) return hipErrorInvalidValue;
@@ -936,36 +817,10 @@ hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s)
     }
     if (a.w_type == NFAI_KQ_MIXED) return q4t_bpw<NFAI_KQ_MIXED, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
     if (a.w_type == NFAI_KQ_MIXED5) return q4t_bpw<NFAI_KQ_MIXED5, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
-    if (a.w_type == NFAI_Q5_K_T16) {
-        switch (a.mode) {
-            case GEMV_PLAIN: return q4t_bpw<NFAI_Q5_K_T16, GEMV_PLAIN>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_RESIDUAL: return q4t_bpw<NFAI_Q5_K_T16, GEMV_RESIDUAL>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_QKV_ROPE: return q4t_bpw<NFAI_Q5_K_T16, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_GATEUP: return q4t_bpw<NFAI_Q5_K_T16, GEMV_GATEUP>(p, bpw, grid, nw * 64, lds, s);
-        }
-    } else if (a.w_type == NFAI_Q8_0_T16) {
-        switch (a.mode) {
-            case GEMV_PLAIN: return q4t_bpw<NFAI_Q8_0_T16, GEMV_PLAIN>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_RESIDUAL: return q4t_bpw<NFAI_Q8_0_T16, GEMV_RESIDUAL>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_QKV_ROPE: return q4t_bpw<NFAI_Q8_0_T16, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_GATEUP: return q4t_bpw<NFAI_Q8_0_T16, GEMV_GATEUP>(p, bpw, grid, nw * 64, lds, s);
-        }
-    } else if (a.w_type == NFAI_Q4_K_T16) {
-        switch (a.mode) {
-            case GEMV_PLAIN: return q4t_bpw<NFAI_Q4_K_T16, GEMV_PLAIN>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_RESIDUAL: return q4t_bpw<NFAI_Q4_K_T16, GEMV_RESIDUAL>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_QKV_ROPE: return q4t_bpw<NFAI_Q4_K_T16, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_GATEUP: return q4t_bpw<NFAI_Q4_K_T16, GEMV_GATEUP>(p, bpw, grid, nw * 64, lds, s);
-        }
-    } else {
-        switch (a.mode) {
-            case GEMV_PLAIN: return q4t_bpw<NFAI_Q6_K_T16, GEMV_PLAIN>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_RESIDUAL: return q4t_bpw<NFAI_Q6_K_T16, GEMV_RESIDUAL>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_QKV_ROPE: return q4t_bpw<NFAI_Q6_K_T16, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
-            case GEMV_GATEUP: return q4t_bpw<NFAI_Q6_K_T16, GEMV_GATEUP>(p, bpw, grid, nw * 64, lds, s);
-        }
-    }
-    return hipErrorInvalidValue;
+    if (a.w_type == NFAI_Q5_K_T16) return q4t_mode<NFAI_Q5_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
+    if (a.w_type == NFAI_Q8_0_T16) return q4t_mode<NFAI_Q8_0_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
+    if (a.w_type == NFAI_Q4_K_T16) return q4t_mode<NFAI_Q4_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
+    return q4t_mode<NFAI_Q6_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
 }
 
 }  // namespace nfai

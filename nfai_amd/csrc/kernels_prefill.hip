@@ -387,7 +387,7 @@ __global__ __launch_bounds__(WM *WN *KS * 64) void k_gemm_f16(const GemmParams p
     gemm_store<BM, BN, WM, WN, EPI, TM, TN>(acc, p, m0, n0, wm, wn, lane, batch);
 }
 
-// ---- dequant-in-LDS GEMM for K-quant weights (T16 layouts of kernels_gemv_kqm.hip) ---------------------------------------
+// ---- dequant-in-LDS GEMM for K-quant weights (T16 layout: t16.h) ---------------------------------------
 // C[M][N] (+R) = A[M][K] fp16 * W[N][K]^T with W in Q4_K / Q6_K blocks: the quantised bytes of a B tile (64 or 128 rows x 64 k:
 // 2.3 - 6.6 KB instead of 8 - 16 KB of fp16) go global -> VGPR, are expanded to fp16 by the thread that loaded them
 // (d * sc * q - dmin * m, resp. d * sc * (q - 32), rounded to fp16 exactly as a separate widening pass would) and written
@@ -467,17 +467,17 @@ __global__ __launch_bounds__(256) void k_gemm_kq(const GemmParams p)
         }
 #pragma unroll
         for (int i = 0; i < BT; i++) {
-            const uint64_t tb = (uint64_t)(wrow[i] >> 4) * NB + blk;
+            const uint64_t tb = t16_tb(wrow[i] >> 4, NB, blk);
             const uint32_t r = wrow[i] & 15;
             if constexpr (QT == NFAI_Q4_K_T16) {
-                b[i].qs = *reinterpret_cast<const GLOBAL_AS u32x4 *>(wbase[i] + tb * 2048 + (part[i] & 1) * 1024 + (c4 * 16 + r) * 16);
-                b[i].hdr = *reinterpret_cast<const GLOBAL_AS u32x4 *>(wbase[i] + wnblk[i] * 128 + tb * 256 + r * 16);
+                b[i].qs = *reinterpret_cast<const GLOBAL_AS u32x4 *>(t16_k4_qs(wbase[i], tb) + (part[i] & 1) * 1024 + (c4 * 16 + r) * 16);
+                b[i].hdr = *reinterpret_cast<const GLOBAL_AS u32x4 *>(t16_k4_hdr(wbase[i], wnblk[i], tb) + r * 16);
             } else {
                 const uint32_t qd = 2 * (c4 & 1) + (part[i] >> 1), G = 2 * (c4 >> 1) + (part[i] & 1);
-                b[i].ql = *reinterpret_cast<const GLOBAL_AS u32x4 *>(wbase[i] + tb * 3072 + (qd & 1) * 1024 + (G * 16 + r) * 16);
-                b[i].qh = *reinterpret_cast<const GLOBAL_AS u32x4 *>(wbase[i] + tb * 3072 + 2048 + (G * 16 + r) * 16);
-                b[i].sc = *reinterpret_cast<const GLOBAL_AS u32x4 *>(wbase[i] + wnblk[i] * 192 + tb * 256 + r * 16);
-                b[i].d = *reinterpret_cast<const GLOBAL_AS uint16_t *>(wbase[i] + wnblk[i] * 208 + tb * 32 + r * 2);
+                b[i].ql = *reinterpret_cast<const GLOBAL_AS u32x4 *>(t16_q6k_q(wbase[i], tb) + (qd & 1) * 1024 + (G * 16 + r) * 16);
+                b[i].qh = *reinterpret_cast<const GLOBAL_AS u32x4 *>(t16_q6k_q(wbase[i], tb) + 2048 + (G * 16 + r) * 16);
+                b[i].sc = *reinterpret_cast<const GLOBAL_AS u32x4 *>(t16_q6k_sc(wbase[i], wnblk[i], tb) + r * 16);
+                b[i].d = *reinterpret_cast<const GLOBAL_AS uint16_t *>(t16_q6k_d(wbase[i], wnblk[i], tb) + r * 2);
             }
         }
     };
@@ -494,11 +494,8 @@ __global__ __launch_bounds__(256) void k_gemm_kq(const GemmParams p)
             f16x8 o[2];
             if constexpr (QT == NFAI_Q4_K_T16) {
                 const float d = h2f_lo(b[i].hdr[0]), dmin = h2f_hi(b[i].hdr[0]);
-                const uint32_t sb = 2 * c4 + (pt >> 1), sh = (sb & 3) * 8;
-                const uint32_t lo8 = (b[i].hdr[1] >> sh) & 0xFFu, mid = (b[i].hdr[2] >> sh) & 0xFFu, hi8 = (b[i].hdr[3] >> sh) & 0xFFu;
-                const bool low = sb < 4;
-                const uint32_t sc = low ? (lo8 & 63u) : ((hi8 & 0xFu) | ((lo8 >> 6) << 4));
-                const uint32_t mn = low ? (mid & 63u) : ((hi8 >> 4) | ((mid >> 6) << 4));
+                uint32_t sc, mn;
+                k4_scale_min(b[i].hdr, 2 * c4 + (pt >> 1), sc, mn);
                 const float d1 = d * (float)sc, m1 = dmin * (float)mn;
                 const uint32_t nsh = (pt >> 1) * 4;  // high nibbles for the odd sub-block
 #pragma unroll
@@ -507,9 +504,8 @@ __global__ __launch_bounds__(256) void k_gemm_kq(const GemmParams p)
                     o[e >> 3][e & 7] = (_Float16)(d1 * (float)q - m1);
                 }
             } else {
-                const uint32_t qd = 2 * (c4 & 1) + (pt >> 1), si = 8 * (c4 >> 1) + (pt & 1) + 2 * qd;
-                const uint32_t sw = si < 8 ? (si < 4 ? b[i].sc[0] : b[i].sc[1]) : (si < 12 ? b[i].sc[2] : b[i].sc[3]);
-                const float dsc = h2f_lo(b[i].d) * (float)(int)(int8_t)((sw >> ((si & 3) * 8)) & 0xFFu);
+                const uint32_t qd = 2 * (c4 & 1) + (pt >> 1);
+                const float dsc = h2f_lo(b[i].d) * (float)q6k_scale(b[i].sc, 8 * (c4 >> 1) + (pt & 1) + 2 * qd);
                 const uint32_t nsh = (qd >> 1) * 4;
 #pragma unroll
                 for (int e = 0; e < 16; e++) {

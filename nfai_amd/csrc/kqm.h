@@ -1,7 +1,10 @@
-// kqm.h — pieces of the int8-MFMA K-quant GEMV (kernels_gemv_kqm.hip: layout, numerics and operand roles are described there)
-// shared with the fused attention + Wo launch (kernels_attn.hip).
+// kqm.h — what the int8-MFMA GEMVs on T16 weights share (kernels_gemv_kqm.hip: one sequence, numerics and operand roles are described
+// there; kernels_gemv_batch_kqm.hip: up to 8 sequences): a wave's step registers and loads per type, the unpack of a step into MFMA B
+// operands, the dot products with their fp32 scale epilogues, and the fixed-point staging of the activations.  The layout itself
+// (plane addresses, block decode) is t16.h.
 #pragma once
 #include "common.h"
+#include "t16.h"
 
 namespace nfai {
 
@@ -39,6 +42,7 @@ struct KqmParams {
 struct Q4T { u32x4 q0, q1, hdr; };
 struct Q8T { u32x4 q[4]; u32x2 d; };
 struct Q5T { u32x4 q0, q1, hdr; u32x2 qh; };
+struct Q6T { u32x4 qla, qlb, qh, sc; uint32_t d; };
 
 __device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t mask, uint32_t bits) { return (a & mask) | bits; }
 
@@ -54,12 +58,11 @@ __device__ __forceinline__ float dpp_add8(float v)  // sum within aligned groups
 // tensor in the T16 layout, `n_tiles` its tiles, NB = super-blocks per row.
 __device__ __forceinline__ Q4T q4t_load_raw(const uint8_t *base, uint64_t n_tiles, uint32_t NB, uint32_t tile, uint32_t blk, uint32_t lane)
 {
-    const uint64_t tb = (uint64_t)tile * NB + blk;
-    const uint64_t nblk = n_tiles * 16 * NB;
+    const uint64_t tb = t16_tb(tile, NB, blk), nblk = t16_nblk(n_tiles, NB);
     Q4T r;
-    r.q0 = load_nt16(base + tb * 2048 + lane * 16);
-    r.q1 = load_nt16(base + tb * 2048 + 1024 + lane * 16);
-    r.hdr = load_nt16(base + nblk * 128 + tb * 256 + (lane & 15) * 16);
+    r.q0 = load_nt16(t16_k4_qs(base, tb) + lane * 16);
+    r.q1 = load_nt16(t16_k4_qs(base, tb) + 1024 + lane * 16);
+    r.hdr = load_nt16(t16_k4_hdr(base, nblk, tb) + (lane & 15) * 16);
     return r;
 }
 
@@ -73,12 +76,11 @@ __device__ __forceinline__ Q4T q4t_load(const KqmParams &p, uint32_t seg, uint32
 // the quants; with the 16 bytes of the row the q|k|v launch at K > 16384 spilled).
 __device__ __forceinline__ Q8T q8t_load_raw(const uint8_t *base, uint64_t n_tiles, uint32_t NB, uint32_t tile, uint32_t blk, uint32_t lane)
 {
-    const uint64_t tb = (uint64_t)tile * NB + blk;
-    const uint64_t nblk = n_tiles * 16 * NB;
+    const uint64_t tb = t16_tb(tile, NB, blk), nblk = t16_nblk(n_tiles, NB);
     Q8T r;
 #pragma unroll
-    for (int h = 0; h < 4; h++) r.q[h] = load_nt16(base + tb * 4096 + h * 1024 + lane * 16);
-    r.d = __builtin_nontemporal_load((const GLOBAL_AS u32x2 *)(base + nblk * 256 + tb * 256 + (lane & 15) * 16 + (lane >> 5) * 8));
+    for (int h = 0; h < 4; h++) r.q[h] = load_nt16(t16_q80_qs(base, tb) + h * 1024 + lane * 16);
+    r.d = __builtin_nontemporal_load((const GLOBAL_AS u32x2 *)(t16_q80_d(base, nblk, tb) + (lane & 15) * 16 + (lane >> 5) * 8));
     return r;
 }
 
@@ -116,16 +118,13 @@ __device__ __forceinline__ float q4t_dot(const Q4T &w, const i32x4 (&af)[4], f32
         dlo = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[0 * 2 + hf], __builtin_bit_cast(i32x4, blo), dlo, 0, 0, 0);
         dhi = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[1 * 2 + hf], __builtin_bit_cast(i32x4, bhi), dhi, 0, 0, 0);
     }
-    // get_scale_min_k4 (ggml) for sub-blocks 2G and 2G+1, branch-free (see kernels_gemv_kq.hip)
+    // scale and min of sub-blocks 2G and 2G+1
     const float d = h2f_lo(w.hdr[0]), dmin = h2f_hi(w.hdr[0]);
     float scv[2], mv[2];
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-        const uint32_t sb = 2 * g + h, sh = (sb & 3) * 8;
-        const uint32_t lo8 = (w.hdr[1] >> sh) & 0xFFu, mid = (w.hdr[2] >> sh) & 0xFFu, hi8 = (w.hdr[3] >> sh) & 0xFFu;
-        const bool low = sb < 4;
-        const uint32_t sc = low ? (lo8 & 63u) : ((hi8 & 0xFu) | ((lo8 >> 6) << 4));
-        const uint32_t mn = low ? (mid & 63u) : ((hi8 >> 4) | ((mid >> 6) << 4));
+        uint32_t sc, mn;
+        k4_scale_min(w.hdr, 2 * g + h, sc, mn);
         scv[h] = d * (float)sc;
         mv[h] = dmin * (float)mn;
     }
@@ -143,13 +142,12 @@ __device__ __forceinline__ float q4t_dot(const Q4T &w, const i32x4 (&af)[4], f32
 // contiguous 512-byte load per wave (14 VGPRs per step).
 __device__ __forceinline__ Q5T q5t_load_raw(const uint8_t *base, uint64_t n_tiles, uint32_t NB, uint32_t tile, uint32_t blk, uint32_t lane)
 {
-    const uint64_t tb = (uint64_t)tile * NB + blk;
-    const uint64_t nblk = n_tiles * 16 * NB;
+    const uint64_t tb = t16_tb(tile, NB, blk), nblk = t16_nblk(n_tiles, NB);
     Q5T r;
-    r.q0 = load_nt16(base + tb * 2048 + lane * 16);
-    r.q1 = load_nt16(base + tb * 2048 + 1024 + lane * 16);
-    r.hdr = load_nt16(base + nblk * 128 + tb * 256 + (lane & 15) * 16);
-    r.qh = __builtin_nontemporal_load((const GLOBAL_AS u32x2 *)(base + nblk * 144 + tb * 512 + lane * 8));
+    r.q0 = load_nt16(t16_k4_qs(base, tb) + lane * 16);
+    r.q1 = load_nt16(t16_k4_qs(base, tb) + 1024 + lane * 16);
+    r.hdr = load_nt16(t16_k4_hdr(base, nblk, tb) + (lane & 15) * 16);
+    r.qh = __builtin_nontemporal_load((const GLOBAL_AS u32x2 *)(t16_q5k_qh(base, nblk, tb) + lane * 8));
     return r;
 }
 
@@ -178,16 +176,13 @@ __device__ __forceinline__ float q5t_dot(const Q5T &w, const i32x4 (&af)[4], f32
         dlo = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[0 * 2 + hf], __builtin_bit_cast(i32x4, blo), dlo, 0, 0, 0);
         dhi = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[1 * 2 + hf], __builtin_bit_cast(i32x4, bhi), dhi, 0, 0, 0);
     }
-    // the Q4_K epilogue: get_scale_min_k4 of sub-blocks 2G and 2G+1, d * sc * sum q x' - dmin * m * sum x'
+    // the Q4_K epilogue: scale and min of sub-blocks 2G and 2G+1, d * sc * sum q x' - dmin * m * sum x'
     const float d = h2f_lo(w.hdr[0]), dmin = h2f_hi(w.hdr[0]);
     float scv[2], mv[2];
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-        const uint32_t sb = 2 * g + h, sh = (sb & 3) * 8;
-        const uint32_t lo8 = (w.hdr[1] >> sh) & 0xFFu, mid = (w.hdr[2] >> sh) & 0xFFu, hi8 = (w.hdr[3] >> sh) & 0xFFu;
-        const bool low = sb < 4;
-        const uint32_t sc = low ? (lo8 & 63u) : ((hi8 & 0xFu) | ((lo8 >> 6) << 4));
-        const uint32_t mn = low ? (mid & 63u) : ((hi8 >> 4) | ((mid >> 6) << 4));
+        uint32_t sc, mn;
+        k4_scale_min(w.hdr, 2 * g + h, sc, mn);
         scv[h] = d * (float)sc;
         mv[h] = dmin * (float)mn;
     }
@@ -198,6 +193,129 @@ __device__ __forceinline__ float q5t_dot(const Q5T &w, const i32x4 (&af)[4], f32
     a = fmaf(scv[1], vhi, a);
     a = fmaf(-mv[1], sums[1], a);
     return a;
+}
+
+// One step of a wave on a Q6_K T16 tensor: the three quant pieces (3 x 1 KiB), the 16 rows' scales (256 B) and d (32 B) of tile-block tb.
+__device__ __forceinline__ Q6T q6t_load_at(const uint8_t *base, uint64_t nblk, uint64_t tb, uint32_t lane)
+{
+    Q6T r;
+    r.qla = load_nt16(t16_q6k_q(base, tb) + lane * 16);
+    r.qlb = load_nt16(t16_q6k_q(base, tb) + 1024 + lane * 16);
+    r.qh = load_nt16(t16_q6k_q(base, tb) + 2048 + lane * 16);
+    r.sc = load_nt16(t16_q6k_sc(base, nblk, tb) + (lane & 15) * 16);
+    r.d = *reinterpret_cast<const GLOBAL_AS uint16_t *>(t16_q6k_d((const GLOBAL_AS uint8_t *)base, nblk, tb) + (lane & 15) * 2);
+    return r;
+}
+
+__device__ __forceinline__ Q6T q6t_load_raw(const uint8_t *base, uint64_t n_tiles, uint32_t NB, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    const uint64_t tb = t16_tb(tile, NB, blk), nblk = t16_nblk(n_tiles, NB);
+    return q6t_load_at(base, nblk, tb, lane);
+}
+
+// (the tensor's pointer is fetched last, as this kernel family was tuned: k_gemv_kqt's schedule follows the order of these argument reads)
+__device__ __forceinline__ Q6T q6t_load(const KqmParams &p, uint32_t seg, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    const uint64_t tb = t16_tb(tile, p.NB, blk), nblk = t16_nblk(p.seg_tiles[seg], p.NB);
+    return q6t_load_at(p.W[seg], nblk, tb, lane);
+}
+
+// 64 weights of one lane: half n = G>>1 of the super-block, columns l = 16*(G&1) .. +15 of all four quarters
+// (ggml dequantize_row_q6_K: quarter 0/2 = low/high nibbles of ql[l], quarter 1/3 = of ql[l+32], bits 2q..2q+1 of qh[l]);
+// one MFMA per quarter = one 16-weight scale group.  sums = sum of x' over each of the four groups.
+__device__ __forceinline__ float q6t_dot(const Q6T &w, const i32x4 (&af)[4], f32x4 sums, uint32_t g)
+{
+    constexpr uint32_t M4 = 0x0F0F0F0Fu, M2 = 0x30303030u;
+    const float d = h2f_lo(w.d);
+    float tot = 0.f;
+#pragma unroll
+    for (int qd = 0; qd < 4; qd++) {
+        const u32x4 ql = (qd & 1) ? w.qlb : w.qla;
+        const u32x4 lo4 = (qd >= 2) ? ((ql >> 4) & M4) : (ql & M4);
+        const u32x4 hs = qd == 0 ? (w.qh << 4) : (qd == 1 ? (w.qh << 2) : (qd == 2 ? w.qh : (w.qh >> 2)));
+        const u32x4 b = (hs & M2) | lo4;  // unsigned 6-bit value per byte
+        const i32x4 dq = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[qd], __builtin_bit_cast(i32x4, b), i32x4{0, 0, 0, 0}, 0, 0, 0);
+        const float v = fmaf((float)dq[2], 65536.0f, fmaf((float)dq[1], 256.0f, (float)dq[0]));
+        // scales[8n + (G&1) + 2*qd] of the row
+        const uint32_t si = 8 * (g >> 1) + (g & 1) + 2 * qd;
+        const uint32_t sw = si < 8 ? (si < 4 ? w.sc[0] : w.sc[1]) : (si < 12 ? w.sc[2] : w.sc[3]);
+        const int sc = (int)(int8_t)((sw >> ((si & 3) * 8)) & 0xFFu);
+        tot = fmaf((float)sc, fmaf(-32.0f, sums[qd], v), tot);
+    }
+    return d * tot;
+}
+
+// ---- a step against several activation vectors (the batched decode): unpack once, then one dot per column ------------------------------
+// The part of q4t_dot / q6t_dot that does not depend on x, done once per step: the four B operands (one byte per weight) and the scales.
+struct KqmW4 { i32x4 b[4]; float scv[2], mv[2]; };   // b[2n + hf]: low (n = 0) / high (n = 1) nibbles of q{hf}, the slot order of the A fragments
+struct KqmW6 { i32x4 b[4]; float sc[4]; float d; };  // b[qd], scales[8n + (G&1) + 2 qd] as floats
+
+__device__ __forceinline__ KqmW4 kqm_unpack(const Q4T &w, uint32_t g)
+{
+    constexpr uint32_t M = 0x0F0F0F0Fu;
+    KqmW4 u;
+    u.b[0] = __builtin_bit_cast(i32x4, w.q0 & M);
+    u.b[1] = __builtin_bit_cast(i32x4, w.q1 & M);
+    u.b[2] = __builtin_bit_cast(i32x4, (w.q0 >> 4) & M);
+    u.b[3] = __builtin_bit_cast(i32x4, (w.q1 >> 4) & M);
+    // scale and min of sub-blocks 2G and 2G+1
+    const float d = h2f_lo(w.hdr[0]), dmin = h2f_hi(w.hdr[0]);
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        uint32_t sc, mn;
+        k4_scale_min(w.hdr, 2 * g + h, sc, mn);
+        u.scv[h] = d * (float)sc;
+        u.mv[h] = dmin * (float)mn;
+    }
+    return u;
+}
+
+__device__ __forceinline__ KqmW6 kqm_unpack(const Q6T &w, uint32_t g)
+{
+    constexpr uint32_t M4 = 0x0F0F0F0Fu, M2 = 0x30303030u;
+    KqmW6 u;
+    u.d = h2f_lo(w.d);
+#pragma unroll
+    for (int qd = 0; qd < 4; qd++) {
+        const u32x4 ql = (qd & 1) ? w.qlb : w.qla;
+        const u32x4 lo4 = (qd >= 2) ? ((ql >> 4) & M4) : (ql & M4);
+        const u32x4 hs = qd == 0 ? (w.qh << 4) : (qd == 1 ? (w.qh << 2) : (qd == 2 ? w.qh : (w.qh >> 2)));
+        u.b[qd] = __builtin_bit_cast(i32x4, (hs & M2) | lo4);  // unsigned 6-bit value per byte
+        const uint32_t si = 8 * (g >> 1) + (g & 1) + 2 * qd;
+        const uint32_t sw = si < 8 ? (si < 4 ? w.sc[0] : w.sc[1]) : (si < 12 ? w.sc[2] : w.sc[3]);
+        u.sc[qd] = (float)(int)(int8_t)((sw >> ((si & 3) * 8)) & 0xFFu);
+    }
+    return u;
+}
+
+// 64 weights of one lane against one column: the arithmetic of q4t_dot / q6t_dot on the unpacked operand
+__device__ __forceinline__ float kqm_dot(const KqmW4 &u, const i32x4 (&af)[4], f32x4 sums)
+{
+    i32x4 dlo = {0, 0, 0, 0}, dhi = {0, 0, 0, 0};
+    dlo = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[0], u.b[0], dlo, 0, 0, 0);
+    dhi = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[2], u.b[2], dhi, 0, 0, 0);
+    dlo = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[1], u.b[1], dlo, 0, 0, 0);
+    dhi = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[3], u.b[3], dhi, 0, 0, 0);
+    // three signed base-256 digits of the fixed-point activations: sum q*x' = S0 + 256*S1 + 65536*S2 (integers, exact)
+    const float vlo = fmaf((float)dlo[2], 65536.0f, fmaf((float)dlo[1], 256.0f, (float)dlo[0]));
+    const float vhi = fmaf((float)dhi[2], 65536.0f, fmaf((float)dhi[1], 256.0f, (float)dhi[0]));
+    float a = u.scv[0] * vlo;
+    a = fmaf(-u.mv[0], sums[0], a);
+    a = fmaf(u.scv[1], vhi, a);
+    a = fmaf(-u.mv[1], sums[1], a);
+    return a;
+}
+
+__device__ __forceinline__ float kqm_dot(const KqmW6 &u, const i32x4 (&af)[4], f32x4 sums)
+{
+    float tot = 0.f;
+#pragma unroll
+    for (int qd = 0; qd < 4; qd++) {
+        const i32x4 dq = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[qd], u.b[qd], i32x4{0, 0, 0, 0}, 0, 0, 0);
+        const float v = fmaf((float)dq[2], 65536.0f, fmaf((float)dq[1], 256.0f, (float)dq[0]));
+        tot = fmaf(u.sc[qd], fmaf(-32.0f, sums[qd], v), tot);
+    }
+    return u.d * tot;
 }
 
 // Fixed-point staging of ONE 256-element super-block of the activation vector by one wave (lane holds elements 4*lane .. +3, after the

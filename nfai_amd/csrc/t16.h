@@ -1,0 +1,134 @@
+// t16.h — the "T16" layout of ggml Q4_K / Q5_K / Q6_K / Q8_0 tensors in HBM: what it is, where every plane's bytes are, and how a
+// block decodes.  The ONE definition: the repack kernels write it, the int8-MFMA GEMVs (kqm.h), the fp16 widening, the dequant-in-LDS
+// GEMM and the embedding gather read it, all through the helpers below.  Part of common.h (included there, behind the vector types
+// and load helpers it uses): include common.h, never this file alone.
+//
+// Repacked once at upload, same bytes as the native blocks.  Rows are grouped in tiles of 16; a "super-block" is 256 weights of one
+// row (one K-quant block, eight Q8_0 blocks), NB of them per row.  The native block is split into planes, one per field; inside a
+// plane the records of (tile, blk) follow each other in the order tb = tile * NB + blk, 16 rows per record:
+//   Q4_K: plane 0  [tile][blk][h:2][lane:64][16 B]  lane = G*16 + r holds qs[32G+16h .. +16) of row 16*tile+r,
+//                  i.e. lane group G owns sub-blocks 2G (low nibbles) and 2G+1 (high nibbles) of its row;
+//         plane 1  [tile][blk][r:16][16 B]          d, dmin, 12 scale bytes of row 16*tile+r.
+//   Q5_K: planes 0 and 1 of Q4_K (same bytes: qs and the 16-byte header), and
+//         plane 2  [tile][blk][lane:64][8 B]        the 64 fifth bits (qh) of the weights lane (G, r) unpacks, in the order of
+//                                                   q5t_dot (kqm.h): one shift and one v_and_or_b32 per four weights.  Word hf of
+//                  lane (G, r) holds, for the weights l = 16hf + 4i + b (b = byte of dword i of q{hf}), bit 2G of qh[l] at 8b + i
+//                  and bit 2G+1 at 8b + 4 + i.
+//   Q6_K: plane 0  [tile][blk][piece:3][lane:64][16 B]  lane = G*16 + r, n = G>>1, lh = G&1:
+//                  piece 0 = ql[64n + 16lh ..+16), piece 1 = ql[64n + 32 + 16lh ..+16), piece 2 = qh[32n + 16lh ..+16);
+//         plane 1  [tile][blk][r:16][16 B]          the 16 int8 scales;
+//         plane 2  [tile][blk][r:16] fp16           d.
+//   Q8_0: plane 0  [tile][blk][h:4][lane:64][16 B]  lane = G*16 + r holds qs bytes 64h + 16G .. +16 of super-block blk of
+//                  row 16*tile+r: 16 weights of ONE 32-block (2h + (G >> 1)), so one d per lane and MFMA;
+//         plane 1  [tile][blk][r:16][16 B]          the eight fp16 d of that row and super-block, d of 32-block b at half
+//                                                   (b & 1) * 4 + (b >> 1): lanes of group G read the 8 bytes of their four d.
+// Every wave-wide load is one contiguous kilobyte (quants), 512 bytes (Q5_K high bits) or 256 bytes (headers).
+// (The planar Q6_K layout of kernels_gemv_kq.hip, for row counts that are not a multiple of 16, is another format.)
+#pragma once
+
+namespace nfai {
+
+// Bytes per row and super-block of every plane: the native ggml block, split up.
+constexpr uint32_t GGML_Q4_K_BLOCK = 144, GGML_Q5_K_BLOCK = 176, GGML_Q6_K_BLOCK = 210, GGML_Q8_0_BLOCK = 34;
+constexpr uint32_t T16_K4_QS = 128, T16_K4_HDR = 16, T16_Q5K_QH = 32;  // Q4_K / Q5_K: qs | d, dmin, scales[12] | qh
+constexpr uint32_t T16_Q6K_Q = 192, T16_Q6K_SC = 16, T16_Q6K_D = 2;    // Q6_K: ql[128] + qh[64] | scales[16] | d
+constexpr uint32_t T16_Q80_QS = 256, T16_Q80_D = 16;                   // Q8_0: 8 x qs[32] | 8 x d
+static_assert(T16_K4_QS + T16_K4_HDR == GGML_Q4_K_BLOCK && T16_K4_QS + T16_K4_HDR + T16_Q5K_QH == GGML_Q5_K_BLOCK &&
+                  T16_Q6K_Q + T16_Q6K_SC + T16_Q6K_D == GGML_Q6_K_BLOCK && T16_Q80_QS + T16_Q80_D == 8 * GGML_Q8_0_BLOCK,
+              "the T16 planes are the bytes of the native blocks (weight_row_bytes)");
+
+// ---- plane addresses: the record of tile-block tb = tile * NB + blk in each plane of the tensor at `base` (P: a byte pointer of any
+// address space; nblk = row-blocks of the tensor).  Pointer in, pointer out, one term per step: the address arithmetic the readers
+// were written with, so the compiler sees what it saw when the offsets were spelled out in place.
+#define T16_ADDR template <class P> __host__ __device__ __forceinline__ P
+__host__ __device__ __forceinline__ uint64_t t16_nblk(uint64_t n_tiles, uint32_t NB) { return n_tiles * 16 * NB; }
+__host__ __device__ __forceinline__ uint64_t t16_tb(uint64_t tile, uint32_t NB, uint32_t blk) { return tile * NB + blk; }
+T16_ADDR t16_k4_qs(P base, uint64_t tb) { return base + tb * (16 * T16_K4_QS); }                                                   // + h * 1024 + lane * 16
+T16_ADDR t16_k4_hdr(P base, uint64_t nblk, uint64_t tb) { return base + nblk * T16_K4_QS + tb * (16 * T16_K4_HDR); }               // + r * 16
+T16_ADDR t16_q5k_qh(P base, uint64_t nblk, uint64_t tb) { return base + nblk * (T16_K4_QS + T16_K4_HDR) + tb * (16 * T16_Q5K_QH); }  // + lane * 8
+T16_ADDR t16_q6k_q(P base, uint64_t tb) { return base + tb * (16 * T16_Q6K_Q); }                                                   // + piece * 1024 + lane * 16
+T16_ADDR t16_q6k_sc(P base, uint64_t nblk, uint64_t tb) { return base + nblk * T16_Q6K_Q + tb * (16 * T16_Q6K_SC); }               // + r * 16
+T16_ADDR t16_q6k_d(P base, uint64_t nblk, uint64_t tb) { return base + nblk * (T16_Q6K_Q + T16_Q6K_SC) + tb * (16 * T16_Q6K_D); }  // + r * 2
+T16_ADDR t16_q80_qs(P base, uint64_t tb) { return base + tb * (16 * T16_Q80_QS); }                                                 // + h * 1024 + lane * 16
+T16_ADDR t16_q80_d(P base, uint64_t nblk, uint64_t tb) { return base + nblk * T16_Q80_QS + tb * (16 * T16_Q80_D); }                // + r * 16
+#undef T16_ADDR
+
+// ---- block decode ------------------------------------------------------------------------------------------------------------------
+// ggml get_scale_min_k4: the 6-bit scale and min of sub-block sb (0..7) of a Q4_K / Q5_K block, branch-free on the header words
+// (hdr[0] = d | dmin, hdr[1..3] = the 12 scale bytes).
+__device__ __forceinline__ void k4_scale_min(const u32x4 hdr, uint32_t sb, uint32_t &sc, uint32_t &mn)
+{
+    const uint32_t sh = (sb & 3) * 8;
+    const uint32_t lo8 = (hdr[1] >> sh) & 0xFFu, mid = (hdr[2] >> sh) & 0xFFu, hi8 = (hdr[3] >> sh) & 0xFFu;
+    const bool low = sb < 4;
+    sc = low ? (lo8 & 63u) : ((hi8 & 0xFu) | ((lo8 >> 6) << 4));
+    mn = low ? (mid & 63u) : ((hi8 >> 4) | ((mid >> 6) << 4));
+}
+
+// The same on the 12 scale bytes in memory (P: a byte pointer of any address space).
+template <class P>
+__device__ __forceinline__ void k4_scale_min_bytes(P scales, uint32_t sb, uint32_t &sc, uint32_t &m)
+{
+    if (sb < 4) { sc = scales[sb] & 63; m = scales[sb + 4] & 63; }
+    else { sc = (scales[sb + 4] & 0xF) | ((scales[sb - 4] >> 6) << 4); m = (scales[sb + 4] >> 4) | ((scales[sb] >> 6) << 4); }
+}
+
+// Q6_K: the int8 scale of 16-weight group si (0..15) from the four scale words of the block.
+__device__ __forceinline__ int q6k_scale(const u32x4 sc, uint32_t si)
+{
+    const uint32_t sw = si < 8 ? (si < 4 ? sc[0] : sc[1]) : (si < 12 ? sc[2] : sc[3]);
+    return (int)(int8_t)((sw >> ((si & 3) * 8)) & 0xFFu);
+}
+
+// Four consecutive elements k .. k+3 (k % 4 == 0) of row `row` of a T16 tensor with E columns and n_rows rows, as fp32: the block
+// exactly as ggml dequantises it (d * sc * q - dmin * m; d * sc * (q - 32); d * q), products and the difference rounded as written.
+__device__ __forceinline__ f32x4 t16_row_load4(const uint8_t *table, int type, uint64_t n_rows, uint64_t row, uint32_t k, uint32_t E)
+{
+    typedef __attribute__((address_space(1))) uint8_t g8;
+    const g8 *t = (const g8 *)table;
+    const uint32_t NB = E / 256, blk = k >> 8, kk = k & 255;
+    const uint64_t tile = row >> 4, r = row & 15, tb = t16_tb(tile, NB, blk), nblk = n_rows * NB;
+    f32x4 out;
+    if (type == NFAI_Q8_0_T16) {
+        const uint32_t ln = ((kk >> 4) & 3) * 16 + (uint32_t)r;
+        const uint32_t q4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t16_q80_qs(t, tb) + (kk >> 6) * 1024 + ln * 16 + (kk & 15));
+        const uint32_t b32 = kk >> 5;  // its d: half (b32 & 1) * 4 + (b32 >> 1) of the row's 16 bytes
+        const float d = (float)reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(t16_q80_d(t, nblk, tb) + r * 16)[(b32 & 1) * 4 + (b32 >> 1)];
+#pragma unroll
+        for (int e = 0; e < 4; e++) out[e] = d * (float)(int8_t)((q4 >> (8 * e)) & 0xFFu);
+    } else if (type == NFAI_Q4_K_T16 || type == NFAI_Q5_K_T16) {
+        const uint32_t sb = kk >> 5, l = kk & 31;
+        const g8 *hdr = t16_k4_hdr(t, nblk, tb) + r * 16;
+        const float d = (float)*reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(hdr);
+        const float dmin = (float)*reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(hdr + 2);
+        uint32_t sc, m;
+        k4_scale_min_bytes(hdr + 4, sb, sc, m);
+        const uint32_t q4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t16_k4_qs(t, tb) + (l >> 4) * 1024 + ((sb >> 1) * 16 + r) * 16 + (l & 15));
+        uint32_t h5 = 0;  // Q5_K: the fifth bits of the four weights at bits 8e of h5
+        if (type == NFAI_Q5_K_T16)
+            h5 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t16_q5k_qh(t, nblk, tb) + ((sb >> 1) * 16 + r) * 8 + (l >> 4) * 4) >>
+                 (4 * (sb & 1) + ((l >> 2) & 3));
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const uint32_t q = (q4 >> (8 * e)) & 0xFFu;
+            const uint32_t q5 = ((sb & 1) ? (q >> 4) : (q & 0xF)) | (((h5 >> (8 * e)) & 1u) << 4);
+            out[e] = d * (float)sc * (float)q5 - dmin * (float)m;
+        }
+    } else {  // NFAI_Q6_K_T16
+        const uint32_t n = kk >> 7, qd = (kk >> 5) & 3, l = kk & 31, lh = l >> 4, b = l & 15;
+        const uint32_t ln = (n * 2 + lh) * 16 + (uint32_t)r;
+        const uint32_t ql4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t16_q6k_q(t, tb) + (qd & 1) * 1024 + ln * 16 + b);
+        const uint32_t qh4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t16_q6k_q(t, tb) + 2048 + ln * 16 + b);
+        const int sc = (int)(int8_t)t16_q6k_sc(t, nblk, tb)[r * 16 + 8 * n + lh + 2 * qd];
+        const float d = (float)reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(t16_q6k_d(t, nblk, tb))[r];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const uint32_t ql = (ql4 >> (8 * e)) & 0xFFu, qh = (qh4 >> (8 * e)) & 0xFFu;
+            const int q = (int)(((qd >= 2) ? (ql >> 4) : (ql & 0xF)) | (((qh >> (2 * qd)) & 3) << 4)) - 32;
+            out[e] = d * (float)sc * (float)q;
+        }
+    }
+    return out;
+}
+
+}  // namespace nfai

@@ -302,7 +302,7 @@ def run_against_oracle(mgr, dims, wq, wref, steps, **variants):
 @pytest.mark.parametrize("mix", ["all_q5_k", "q5_k_m"])
 def test_model_q5_k_graph_eager_unfused(mgr, dims, mix):
     """Graph, eager and the unfused 1:1 chain against OracleLlama: greedy tokens identical, logits within 5e-4 * max(1, |logit|).
-    all_q5_k: a Q5_K token_embd (through the q|k|v launch's BEGIN prologue in graph / eager, k_embed_q5t unfused) and, on TINY, a
+    all_q5_k: a Q5_K token_embd (through the q|k|v launch's BEGIN prologue in graph / eager, k_embed_t16 unfused) and, on TINY, a
     tied Q5_K lm_head.  q5_k_m: llama.cpp's mix; one block of each dims keeps attn_v in Q6_K (the mixed q|k|v launch)."""
     wq, wref = quant_weights(dims, 61, mix)
     models = run_against_oracle(mgr, dims, wq, wref, 24, graph={}, eager={"graph": False}, unfused={"unfused": True})
