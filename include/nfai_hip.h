@@ -42,6 +42,7 @@ typedef uint64_t nfai_buf_t;
 typedef uint64_t nfai_model_t;
 typedef uint64_t nfai_pp_t;
 typedef uint64_t nfai_batch_t;
+typedef uint64_t nfai_window_t;
 
 enum nfai_status {
     NFAI_OK = 0,
@@ -395,6 +396,55 @@ int32_t nfai_hip_llama_batch_bytes_per_token(nfai_batch_t batch, uint64_t *total
  * counterpart: its loop LlamaModel.cs:116-125 is not instrumented). */
 int32_t nfai_hip_llama_batch_profile_step(nfai_batch_t batch, const uint32_t *tokens /* [n] */, float *ms_by_class /* 8 */,
                                           uint32_t *launches_by_class /* 8 */);
+
+/* ---- window: up to 8 CONSECUTIVE positions of one sequence in ONE pass over the weights (lossless greedy speculative decoding).
+ *      The reference emits one token per pass of the loop LlamaModel.cs:116-125; with SamplingUtils.ArgMax (SamplingUtils.cs:43-57)
+ *      in place of TopP the next tokens are a function of the sequence alone, so guessed continuations (drafts) can be run as extra
+ *      columns of the batched kernels and kept exactly as far as the model's own ArgMax agrees.  The columns share ONE model: its
+ *      weights, its KV cache (the window attention reads the cached prefix once for all columns, kernels_attn_window.hip), its
+ *      position word, token word and ring. ---- */
+/* ≙ preparing to run up to max_tokens passes of the loop LlamaModel.cs:116-125 of ONE LlamaModel at once.  max_tokens in [2, 8].
+ * flags: 0 (all matrices NFAI_F16) or NFAI_BATCH_QUANT (all matrices Q4_K / Q6_K).  The model is admitted as _batch_create /
+ * _batch_create_ex admit a member, with the same answers: NFAI_ERR_INVALID for a dead handle, max_tokens outside [2, 8], unknown flag
+ * bits, a model not finalized; NFAI_ERR_UNSUPPORTED, naming tensor and ggml type, for a pipeline stage, the 1:1 or engine path,
+ * Q5_K / Q8_0 matrices, fp16 and quantised matrices in one model, quantised rows % 16 != 0, a shape the kernels' LDS plan does not
+ * hold.  The window owns the columns' activation vectors, workspaces, token / draft / result words, pinned staging and its graphs
+ * (one per column count, captured on first use); no weights, no KV cache.  The model stays a normal model: _decode_step, _ingest,
+ * _set_pos, _read_kv, _pos between window calls see, and are seen by, the window.  _read: logits are what the model's OWN last token
+ * left (a window's logits are returned by the window calls); the hidden state (which = 0) is that of the last token the model kept,
+ * whichever path ran it: after a window call the last emitted column's, held by that window until the model's next token or the
+ * window's destruction (then the model's own vector again). */
+int32_t nfai_hip_llama_window_create(nfai_model_t model, uint32_t max_tokens, uint32_t flags, nfai_window_t *out);
+/* Frees the window's memory and graphs; the model is not touched (≙ leaving the loop LlamaModel.cs:116-125: the model lives on). */
+int32_t nfai_hip_llama_window_destroy(nfai_window_t window);
+/* ≙ t passes of the loop body LlamaModel.cs:116-125 on the caller's tokens: column i carries tokens[i] at position p + i (p = the
+ * model's position word on the device): RoPE at p + i, its K / V row written at p + i of the model's cache, attention over rows
+ * 0 .. p + i, its own logits and ArgMax (SamplingUtils.cs:55-56: the first index of the maximum).  1 <= t <= max_tokens.  The
+ * position advances by t, the token word is the last column's ArgMax, the ring takes all t.  Column i's logits do not depend on t nor
+ * on the tokens of the columns after it, bit for bit.  Blocking: ONE hipGraphLaunch and one synchronisation; logits_host adds t
+ * device-to-host copies of one row each in front of that synchronisation.  logits_host: [t][n_vocab] fp32 or NULL; argmax: [t] or NULL.  p + t past the KV capacity: NFAI_ERR_KV_FULL before anything is enqueued.  A model
+ * destroyed or re-finalized since _window_create: NFAI_ERR_INVALID. */
+int32_t nfai_hip_llama_window_step(nfai_window_t window, const uint32_t *tokens /* [t] */, uint32_t t, float *logits_host /* [t][V] or NULL */,
+                                   uint32_t *argmax /* [t] or NULL */);
+/* ≙ 1 to k + 1 passes of the loop LlamaModel.cs:116-125 with SamplingUtils.ArgMax (SamplingUtils.cs:43-57), decided by the model:
+ * the columns are token, draft[0 .. k - 1] (0 <= k <= max_tokens - 1); with a_i column i's ArgMax, acc is the largest j with
+ * draft[i] == a_i for all i < j.  *n_out = acc + 1, tokens_out[0 .. acc] = a_0 .. a_acc: exactly the tokens acc + 1 plain greedy
+ * steps would emit.  Afterwards the model is where feeding token, a_0 .. a_(acc-1) one by one would have left it: position
+ * p + acc + 1, token word a_acc, ring extended by the emitted tokens; K / V rows at or above the position hold rejected drafts, are
+ * never read and are overwritten by the next step.  The rule runs on the device in the tail of the lm_head launch: one graph launch,
+ * one synchronisation.  logits_host: [k + 1][n_vocab] (all columns) or NULL; tokens_out: [k + 1].  k = 0 is a plain greedy step.
+ * Errors as _window_step (the capacity must hold all k + 1 columns). */
+int32_t nfai_hip_llama_window_verify(nfai_window_t window, uint32_t token, const uint32_t *draft /* [k] */, uint32_t k,
+                                     float *logits_host /* [k+1][V] or NULL */, uint32_t *tokens_out /* [k+1] */, uint32_t *n_out);
+/* Algorithmic HBM bytes of ONE window step of t tokens at the model's position p: every weight once, t embedding
+ * rows, the p cached K / V rows ONCE, column i's i + 1 window rows, t rows written — against t times
+ * nfai_hip_llama_bytes_per_token for t passes of LlamaModel.cs:116-125. */
+int32_t nfai_hip_llama_window_bytes_per_step(nfai_window_t window, uint32_t t, uint64_t *total);
+/* One window step of t tokens (as _window_step without results: the position advances by t) launch by launch between hipEvents:
+ * device time and launch count by kernel class, the ids of nfai_hip_llama_profile_step (slow path, for tools/spec_decode_bench.py; the
+ * reference's loop LlamaModel.cs:116-125 is not instrumented). */
+int32_t nfai_hip_llama_window_profile_step(nfai_window_t window, const uint32_t *tokens /* [t] */, uint32_t t, float *ms_by_class /* 8 */,
+                                           uint32_t *launches_by_class /* 8 */);
 
 /* ---- layer pipeline across GPUs (no reference counterpart: the reference is single-device, it takes the last enumerated
  *      Vulkan device, VulkanHelper.cs:149-150).  One process per GPU owns a contiguous range of TransformerBlocks (a slice of

@@ -122,6 +122,12 @@ SIGNATURES = {
     "nfai_hip_llama_batch_greedy": [H, C.POINTER(u32), u32, C.POINTER(u32)],
     "nfai_hip_llama_batch_bytes_per_token": [H, C.POINTER(u64)],
     "nfai_hip_llama_batch_profile_step": [H, C.POINTER(u32), C.POINTER(f32), C.POINTER(u32)],
+    "nfai_hip_llama_window_create": [H, u32, u32, C.POINTER(H)],
+    "nfai_hip_llama_window_destroy": [H],
+    "nfai_hip_llama_window_step": [H, C.POINTER(u32), u32, C.POINTER(f32), C.POINTER(u32)],
+    "nfai_hip_llama_window_verify": [H, u32, C.POINTER(u32), u32, C.POINTER(f32), C.POINTER(u32), C.POINTER(u32)],
+    "nfai_hip_llama_window_bytes_per_step": [H, u32, C.POINTER(u64)],
+    "nfai_hip_llama_window_profile_step": [H, C.POINTER(u32), u32, C.POINTER(f32), C.POINTER(u32)],
     "nfai_hip_pp_unique_id": [C.POINTER(C.c_uint8)],
     "nfai_hip_pp_init": [H, u32, u32, C.POINTER(C.c_uint8), C.POINTER(H)],
     "nfai_hip_pp_destroy": [H],

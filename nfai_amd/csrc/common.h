@@ -283,6 +283,7 @@ struct BatchGemvArgs {
     uint64_t kv_head_stride[BATCH_MAX] = {};
     uint32_t cap[BATCH_MAX] = {};
     const uint32_t *pos[BATCH_MAX] = {};
+    uint32_t pos_off[BATCH_MAX] = {};  // column b works at position pos[b][0] + pos_off[b]: zeros for a batch, b for a window (one position word)
     uint64_t kv_pos_stride = 0;
     int kv_type = NFAI_F32;
     const float *freqs = nullptr;
@@ -293,8 +294,15 @@ struct BatchGemvArgs {
     uint32_t *am_tok_batch = nullptr;  // [BATCH_MAX]: the batch's token words (next step's input)
     uint32_t *am_tok[BATCH_MAX] = {}, *am_pos[BATCH_MAX] = {}, *am_ring[BATCH_MAX] = {};
     uint32_t am_ring_len = 0;
+    // GEMV_PLAIN of a window (non-null): the columns are consecutive positions of ONE sequence (am_tok / am_pos / am_ring of column 0)
+    // and the tail applies the accept rule of greedy speculative decoding instead of the per-member bookkeeping (win_tail below).
+    // win_ctl: [0..7] draft tokens, [8] their count k (0xFFFFFFFF: keep every column); the count of emitted tokens goes to
+    // am_tok_batch[WIN_NOUT].
+    const uint32_t *win_ctl = nullptr;
     uint32_t n_cu = 256;
 };
+constexpr uint32_t WIN_NOUT = BATCH_MAX + 1;   // (word BATCH_MAX is the error word of the q|k|v launches)
+constexpr uint32_t WIN_ALL = 0xFFFFFFFFu;
 constexpr size_t batch_argmax_bytes() { return (size_t)BATCH_MAX * 1024 * 8 + 256; }
 bool batch_gemv_ok(const BatchGemvArgs &a);   // shape rules of launch_batch_gemv (checked by nfai_hip_llama_batch_create)
 hipError_t launch_batch_gemv(const BatchGemvArgs &a, hipStream_t s);
@@ -313,6 +321,22 @@ struct BatchAttnArgs {
 };
 size_t batch_attn_bytes(uint32_t H, uint32_t D);
 hipError_t launch_batch_attn(const BatchAttnArgs &a, hipStream_t s);
+// Attention of a window (kernels_attn_window.hip): n query columns at the consecutive positions pos[0] + i of ONE cache; column i
+// attends to rows 0 .. pos[0] + i.  The rows below pos[0] are read once per kv head for all columns.
+struct WindowAttnArgs {
+    uint32_t n = 0;
+    const float *q[BATCH_MAX] = {};
+    float *o[BATCH_MAX] = {};
+    const void *kc = nullptr, *vc = nullptr;
+    uint64_t kv_head_stride = 0, kv_pos_stride = 0;
+    uint32_t cap = 0;
+    const uint32_t *pos = nullptr;
+    int kv_type = NFAI_F32;
+    uint32_t H = 0, Hkv = 0, D = 0;
+    void *work = nullptr;              // window_attn_bytes(), zeroed once
+};
+size_t window_attn_bytes(uint32_t H, uint32_t D);
+hipError_t launch_window_attn(const WindowAttnArgs &a, hipStream_t s);
 // x[b] = row tok[b] of the fp16 embedding table, widened (TokenEmbedShader.cs:131-159), b < n
 hipError_t launch_batch_embed(const void *table, uint64_t n_rows, uint32_t E, const uint32_t *tok, float *const *x, uint32_t n, hipStream_t s);
 // The same launches on Q4_K / Q6_K matrices in the T16 layout (kernels_gemv_batch_kqm.hip): W[i] are T16 tensors of ONE type (a q|k|v of
@@ -563,6 +587,28 @@ constexpr uint32_t BEGIN_CS_WORDS = 128;  // LDS words of that table (head_dim <
 // ---- "first index of the largest value" across lanes / waves / workgroups (SamplingUtils.ArgMax, SamplingUtils.cs:55-56: values.Max()
 //      then IndexOf: the LOWEST index among equal maxima) ---------------------------------------------------------------------------
 __device__ __forceinline__ bool topk_better(float av, uint32_t ai, float bv, uint32_t bi) { return av > bv || (av == bv && ai < bi); }
+
+// The lm_head tail of a window (one thread of the workgroup whose ticket is last; am[i] = ArgMax of column i, in LDS): the accept
+// rule of greedy speculative decoding.  Column 0 carried the token just sampled, column i > 0 the draft ctl[i - 1]; acc = the number
+// of leading drafts that ARE the model's own choice (ctl[i] == am[i] for all i < acc, acc <= k), so am[0 .. acc] are exactly the
+// tokens acc + 1 passes of the loop LlamaModel.cs:116-125 with SamplingUtils.ArgMax (SamplingUtils.cs:43-57) would have emitted.
+// The sequence is left as those passes would have left it: ring extended by am[0 .. acc], token word am[acc], position + acc + 1 (the
+// K / V rows of the rejected columns stay above the position, where nothing reads them).  k = WIN_ALL keeps every column (a
+// multi-token step: the caller's tokens are the sequence).
+__device__ __forceinline__ void win_tail(const uint32_t *am, uint32_t n, const uint32_t *ctl, uint32_t *out, uint32_t *tok, uint32_t *pos,
+                                         uint32_t *ring, uint32_t ring_len)
+{
+    const uint32_t k = ctl[BATCH_MAX];
+    const uint32_t lim = k == WIN_ALL ? n - 1 : (k < n - 1 ? k : n - 1);
+    uint32_t acc = 0;
+    while (acc < lim && (k == WIN_ALL || ctl[acc] == am[acc])) acc++;
+    const uint32_t pp = pos[0];
+    for (uint32_t i = 0; i < n; i++) out[i] = am[i];
+    for (uint32_t i = 0; i <= acc; i++) ring[(pp + i) % ring_len] = am[i];
+    out[WIN_NOUT] = acc + 1;
+    tok[0] = am[acc];
+    pos[0] = pp + acc + 1;
+}
 
 __device__ __forceinline__ void wave_best(float &v, uint32_t &i)
 {

@@ -57,6 +57,7 @@ struct BKqParams {
     uint64_t head_stride[BATCH_MAX];
     uint32_t cap[BATCH_MAX];
     const uint32_t *pos[BATCH_MAX];
+    uint32_t pos_off[BATCH_MAX];   // zeros for a batch; a window's column b sits b positions past the one position word
     uint64_t pos_stride;
     int kv_f16;
     const float *freqs;
@@ -68,6 +69,7 @@ struct BKqParams {
     uint32_t *tok_batch;
     uint32_t *tok[BATCH_MAX], *pos_inc[BATCH_MAX], *ring[BATCH_MAX];
     uint32_t ring_len;
+    const uint32_t *win_ctl;   // non-null: the columns are one sequence's window (win_tail, common.h)
 };
 
 template <int MODE>
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if constexpr (MODE == GEMV_QKV_ROPE) {
 #pragma unroll
         for (int b = 0; b < B; b++) {
-            posv[b] = p.pos[b][0];
+            posv[b] = p.pos[b][0] + p.pos_off[b];
             pos_ok[b] = posv[b] < p.cap[b];
             if (!pos_ok[b] && (uint32_t)b < p.n && blockIdx.x == 0 && threadIdx.x == 0) p.err[0] = 0x10000u | (uint32_t)b;
         }
@@ -403,13 +405,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 }
                 wave_best(v, i);
                 if (lane == 0) {
-                    p.tok_batch[b] = i;
-                    p.tok[b][0] = i;
-                    const uint32_t pp = p.pos_inc[b][0];
-                    p.ring[b][pp % p.ring_len] = i;
-                    p.pos_inc[b][0] = pp + 1;
+                    if (p.win_ctl) {
+                        last[8 + b] = i;   // the accept rule needs every column's choice
+                    } else {
+                        p.tok_batch[b] = i;
+                        p.tok[b][0] = i;
+                        const uint32_t pp = p.pos_inc[b][0];
+                        p.ring[b][pp % p.ring_len] = i;
+                        p.pos_inc[b][0] = pp + 1;
+                    }
                 }
             }
+        }
+        if (p.win_ctl) {   // (uniform over the launch)
+            __syncthreads();
+            if (threadIdx.x == 0) win_tail(last + 8, p.n, p.win_ctl, p.tok_batch, p.tok[0], p.pos_inc[0], p.ring[0], p.ring_len);
         }
         if (threadIdx.x == 0) __hip_atomic_store(p.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm (stream-ordered with the next launch)
     }
@@ -515,7 +525,7 @@ hipError_t launch_batch_gemv_kq(const BatchKqArgs &a, hipStream_t s)
     for (uint32_t b = 0; b < BATCH_MAX; b++) {
         const uint32_t c = b < a.n ? b : 0;   // dead columns carry column 0's pointers (nothing is read or stored through them)
         p.x[b] = a.x[c]; p.y[b] = a.y[c]; p.res[b] = a.res[c];
-        p.kc[b] = a.kc[c]; p.vc[b] = a.vc[c]; p.head_stride[b] = a.kv_head_stride[c]; p.cap[b] = a.cap[c]; p.pos[b] = a.pos[c];
+        p.kc[b] = a.kc[c]; p.vc[b] = a.vc[c]; p.head_stride[b] = a.kv_head_stride[c]; p.cap[b] = a.cap[c]; p.pos[b] = a.pos[c]; p.pos_off[b] = a.pos_off[c];
         p.tok[b] = a.am_tok[c]; p.pos_inc[b] = a.am_pos[c]; p.ring[b] = a.am_ring[c];
         if (!p.x[b] || !p.y[b]) return hipErrorInvalidValue;
         if (a.mode == GEMV_RESIDUAL && !p.res[b]) return hipErrorInvalidValue;
@@ -530,7 +540,7 @@ hipError_t launch_batch_gemv_kq(const BatchKqArgs &a, hipStream_t s)
         p.part_v = static_cast<float *>(a.am_work);
         p.part_i = reinterpret_cast<uint32_t *>(p.part_v + BATCH_MAX * BK_MAX_GRID);
         p.ticket = p.part_i + BATCH_MAX * BK_MAX_GRID;
-        p.tok_batch = a.am_tok_batch; p.ring_len = a.am_ring_len;
+        p.tok_batch = a.am_tok_batch; p.ring_len = a.am_ring_len; p.win_ctl = a.win_ctl;
     }
     const bool norm = a.gamma != nullptr;
     if (a.w_type == NFAI_Q6_K_T16) return dispatch_bkq_b<NFAI_Q6_K_T16>(p, pl, a.mode, norm, s);

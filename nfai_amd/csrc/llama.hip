@@ -1940,7 +1940,20 @@ struct Batch {
     uint32_t *h_pin = nullptr;     // [0..7] tokens in | [16..24] token words + error word out
     hipGraph_t g_step = nullptr, g_body = nullptr;
     hipGraphExec_t x_step = nullptr, x_body = nullptr;
+    // column i's activation vectors: member i's own (a batch), or the window's (Window below: every column is mem[0])
+    float *cx[BATCH_MAX] = {}, *ch[BATCH_MAX] = {}, *cq[BATCH_MAX] = {}, *catt[BATCH_MAX] = {}, *cact[BATCH_MAX] = {}, *clog[BATCH_MAX] = {};
+    const uint32_t *d_in = nullptr;   // the step's token words (a batch: d_tok, where the tail leaves the next step's)
+    // A window (nfai_hip_llama_window_create, magic 'NFWN'): up to max_tokens columns at consecutive positions of mem[0]; n is the
+    // column count of the call at hand.  d_tok: [0..7] ArgMax words, [8] error word, [9] emitted count | [32..39] token words in,
+    // [40..47] drafts, [48] draft count; h_pin mirrors it ([0..16] in, [32..41] out).  One graph per column count, captured on first use.
+    bool window = false;
+    uint32_t max_tokens = 0;
+    float *w_act = nullptr;                       // the columns' activation vectors, w_act_floats in all
+    size_t w_act_floats = 0;
+    hipGraph_t wg[BATCH_MAX + 1] = {};
+    hipGraphExec_t wx[BATCH_MAX + 1] = {};
 };
+constexpr uint32_t WIN_MAGIC = 0x4E46574E, WIN_IN = 32;
 
 Batch *batch_of(nfai_batch_t h)
 {
@@ -1988,7 +2001,7 @@ struct BatchOps {
         a.K = d.E; a.mode = GEMV_QKV_ROPE; a.gamma = static_cast<const float *>(L.attn_norm.ptr);
         for (uint32_t i = 0; i < bt->n; i++) {
             Model *m = bt->mem[i];
-            a.x[i] = m->x; a.y[i] = m->q;
+            a.x[i] = bt->cx[i]; a.y[i] = bt->cq[i]; a.pos_off[i] = bt->window ? i : 0u;
             a.kc[i] = m->layers[l].kcache; a.vc[i] = m->layers[l].vcache;
             a.kv_head_stride[i] = m->kv_head_stride; a.cap[i] = m->d.C; a.pos[i] = m->d_pos;
         }
@@ -2004,7 +2017,7 @@ struct BatchOps {
         a.n = bt->n;
         for (uint32_t i = 0; i < bt->n; i++) {
             Model *m = bt->mem[i];
-            a.q[i] = m->q; a.o[i] = m->att; a.kc[i] = m->layers[l].kcache; a.vc[i] = m->layers[l].vcache;
+            a.q[i] = bt->cq[i]; a.o[i] = bt->catt[i]; a.kc[i] = m->layers[l].kcache; a.vc[i] = m->layers[l].vcache;
             a.kv_head_stride[i] = m->kv_head_stride; a.cap[i] = m->d.C; a.pos[i] = m->d_pos;
         }
         a.kv_pos_stride = m0->kv_pos_stride; a.kv_type = m0->kv_f16 ? NFAI_F16 : NFAI_F32;
@@ -2017,7 +2030,7 @@ struct BatchOps {
         Model *m0 = bt->mem[0];
         const Layer &L = m0->layers[l];
         a.W[0] = L.wo.ptr; a.seg_rows[0] = (uint32_t)L.wo.rows; a.K = m0->d.H * m0->d.D; a.mode = GEMV_RESIDUAL;
-        for (uint32_t i = 0; i < bt->n; i++) { Model *m = bt->mem[i]; a.x[i] = m->att; a.res[i] = m->x; a.y[i] = m->h; }
+        for (uint32_t i = 0; i < bt->n; i++) { a.x[i] = bt->catt[i]; a.res[i] = bt->cx[i]; a.y[i] = bt->ch[i]; }
         return a;
     }
     BatchGemvArgs gateup(size_t l) const
@@ -2027,7 +2040,7 @@ struct BatchOps {
         const Layer &L = m0->layers[l];
         a.W[0] = L.wgate.ptr; a.W[1] = L.wup.ptr; a.seg_rows[0] = (uint32_t)L.wgate.rows; a.seg_rows[1] = (uint32_t)L.wup.rows;
         a.K = m0->d.E; a.mode = GEMV_GATEUP; a.gamma = static_cast<const float *>(L.ffn_norm.ptr);
-        for (uint32_t i = 0; i < bt->n; i++) { Model *m = bt->mem[i]; a.x[i] = m->h; a.y[i] = m->act; }
+        for (uint32_t i = 0; i < bt->n; i++) { a.x[i] = bt->ch[i]; a.y[i] = bt->cact[i]; }
         return a;
     }
     BatchGemvArgs down(size_t l) const
@@ -2036,7 +2049,7 @@ struct BatchOps {
         Model *m0 = bt->mem[0];
         const Layer &L = m0->layers[l];
         a.W[0] = L.wdown.ptr; a.seg_rows[0] = (uint32_t)L.wdown.rows; a.K = m0->d.F; a.mode = GEMV_RESIDUAL;
-        for (uint32_t i = 0; i < bt->n; i++) { Model *m = bt->mem[i]; a.x[i] = m->act; a.res[i] = m->h; a.y[i] = m->x; }
+        for (uint32_t i = 0; i < bt->n; i++) { a.x[i] = bt->cact[i]; a.res[i] = bt->ch[i]; a.y[i] = bt->cx[i]; }
         return a;
     }
     BatchGemvArgs head() const
@@ -2048,10 +2061,23 @@ struct BatchOps {
         a.gamma = static_cast<const float *>(m0->output_norm.ptr);
         for (uint32_t i = 0; i < bt->n; i++) {
             Model *m = bt->mem[i];
-            a.x[i] = m->x; a.y[i] = m->logits;
+            a.x[i] = bt->cx[i]; a.y[i] = bt->clog[i];
             a.am_tok[i] = m->d_tok; a.am_pos[i] = m->d_pos; a.am_ring[i] = m->d_ring;
         }
         a.am_work = bt->d_am; a.am_tok_batch = bt->d_tok; a.am_ring_len = RING_LEN;
+        if (bt->window && bt->d_in) a.win_ctl = bt->d_in + BATCH_MAX;   // drafts and their count, behind the token words
+        return a;
+    }
+    WindowAttnArgs wattn(size_t l) const
+    {
+        WindowAttnArgs a;
+        Model *m = bt->mem[0];
+        a.n = bt->n;
+        for (uint32_t i = 0; i < bt->n; i++) { a.q[i] = bt->cq[i]; a.o[i] = bt->catt[i]; }
+        a.kc = m->layers[l].kcache; a.vc = m->layers[l].vcache;
+        a.kv_head_stride = m->kv_head_stride; a.kv_pos_stride = m->kv_pos_stride; a.cap = m->d.C; a.pos = m->d_pos;
+        a.kv_type = m->kv_f16 ? NFAI_F16 : NFAI_F32;
+        a.H = m->d.H; a.Hkv = m->d.Hkv; a.D = m->d.D; a.work = bt->d_attn;
         return a;
     }
 };
@@ -2108,25 +2134,26 @@ int enqueue_batch(Batch *bt, float *ms = nullptr, uint32_t *cnt = nullptr)
     };
 #define B_TRY(c, expr) S_TRY(run(c, [&]() -> hipError_t { return (expr); }))
     float *xs[BATCH_MAX] = {};
-    for (uint32_t i = 0; i < bt->n; i++) xs[i] = bt->mem[i]->x;
+    for (uint32_t i = 0; i < bt->n; i++) xs[i] = bt->cx[i];
+    auto attn = [&](size_t l) { return bt->window ? launch_window_attn(ops.wattn(l), s) : launch_batch_attn(ops.attn(l), s); };
     if (bt->quant) {   // 5 launches per block, 6 where q|k|v is split by type
-        B_TRY(KC_OTHER, launch_batch_embed_kq(m0->token_embd.ptr, m0->token_embd.type, m0->token_embd.rows, m0->d.E, bt->d_tok, xs, bt->n, s));
+        B_TRY(KC_OTHER, launch_batch_embed_kq(m0->token_embd.ptr, m0->token_embd.type, m0->token_embd.rows, m0->d.E, bt->d_in, xs, bt->n, s));
         for (size_t l = 0; l < m0->layers.size(); l++) {
             const Layer &L = m0->layers[l];
             BatchKqArgs qkv[2];
             const int nq = batch_qkv_kq(ops, l, qkv);
             for (int j = 0; j < nq; j++) B_TRY(KC_QKV, launch_batch_gemv_kq(qkv[j], s));
-            B_TRY(KC_ATTN, launch_batch_attn(ops.attn(l), s));
+            B_TRY(KC_ATTN, attn(l));
             B_TRY(KC_WO, launch_batch_gemv_kq(batch_kq(ops.wo(l), L.wo.type), s));
             B_TRY(KC_GATEUP, launch_batch_gemv_kq(batch_kq(ops.gateup(l), L.wgate.type), s));
             B_TRY(KC_DOWN, launch_batch_gemv_kq(batch_kq(ops.down(l), L.wdown.type), s));
         }
         B_TRY(KC_LMHEAD, launch_batch_gemv_kq(batch_kq(ops.head(), (m0->output.ptr ? m0->output : m0->token_embd).type), s));
     } else {
-        B_TRY(KC_OTHER, launch_batch_embed(m0->token_embd.ptr, m0->token_embd.rows, m0->d.E, bt->d_tok, xs, bt->n, s));
+        B_TRY(KC_OTHER, launch_batch_embed(m0->token_embd.ptr, m0->token_embd.rows, m0->d.E, bt->d_in, xs, bt->n, s));
         for (size_t l = 0; l < m0->layers.size(); l++) {
             B_TRY(KC_QKV, launch_batch_gemv(ops.qkv(l), s));
-            B_TRY(KC_ATTN, launch_batch_attn(ops.attn(l), s));
+            B_TRY(KC_ATTN, attn(l));
             B_TRY(KC_WO, launch_batch_gemv(ops.wo(l), s));
             B_TRY(KC_GATEUP, launch_batch_gemv(ops.gateup(l), s));
             B_TRY(KC_DOWN, launch_batch_gemv(ops.down(l), s));
@@ -2177,6 +2204,9 @@ void batch_free(Batch *bt)
     if (bt->g_step) hipGraphDestroy(bt->g_step);
     if (bt->x_body) hipGraphExecDestroy(bt->x_body);
     if (bt->g_body) hipGraphDestroy(bt->g_body);
+    for (hipGraphExec_t x : bt->wx) if (x) hipGraphExecDestroy(x);
+    for (hipGraph_t g : bt->wg) if (g) hipGraphDestroy(g);
+    if (bt->w_act) hipFree(bt->w_act);
     if (bt->d_tok) hipFree(bt->d_tok);
     if (bt->d_am) hipFree(bt->d_am);
     if (bt->d_attn) hipFree(bt->d_attn);
@@ -2202,11 +2232,14 @@ int batch_device_failed(Batch *bt, uint32_t code, const char *fn)
 }  // namespace
 
 // fn: the entry point's name in messages.  flags: NFAI_BATCH_* (0 = the fp16 batch of nfai_hip_llama_batch_create).
-static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out, const char *fn)
+// win_tokens > 0 (nfai_hip_llama_window_create, n = 1): the one model is admitted as a batch admits a member, and the object made is a
+// window of win_tokens columns over it.
+static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out, const char *fn, uint32_t win_tokens = 0)
 {
     if (!models || !out) return fail(NFAI_ERR_INVALID, "%s: null argument", fn);
     if (flags & ~(uint32_t)NFAI_BATCH_QUANT) return fail(NFAI_ERR_INVALID, "%s: invalid flags 0x%x (known: NFAI_BATCH_QUANT = 0x%x)", fn, flags, NFAI_BATCH_QUANT);
     bool quant = false;
+    const char *obj = win_tokens ? "window" : "batch";
     if (n < 1 || n > BATCH_MAX) return fail(NFAI_ERR_INVALID, "%s: invalid n = %u (a batch holds 1 to %u models)", fn, n, BATCH_MAX);
     Model *mem[BATCH_MAX] = {};
     for (uint32_t i = 0; i < n; i++) {
@@ -2221,15 +2254,18 @@ static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t fl
     HIP_TRY(hipSetDevice(m0->ctx->device));
     for (uint32_t i = 0; i < n; i++) {
         Model *m = mem[i];
-        if (!m->finalized) return fail(NFAI_ERR_INVALID, "%s: invalid member %u: call nfai_hip_llama_finalize first", fn, i);
+        char who[24];   // in messages: "member i" of a batch, "the model" of a window
+        if (win_tokens) snprintf(who, sizeof who, "the model");
+        else snprintf(who, sizeof who, "member %u", i);
+        if (!m->finalized) return fail(NFAI_ERR_INVALID, "%s: invalid %s: call nfai_hip_llama_finalize first", fn, who);
         if (!(m->first_stage && m->last_stage))
-            return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u is a pipeline stage (blocks [%u, %u) of %u); a batch takes whole models", fn, i,
-                        m->d.layer_begin, m->d.layer_end, m->d.L);
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: %s is a pipeline stage (blocks [%u, %u) of %u); a %s takes whole models", fn, who,
+                        m->d.layer_begin, m->d.layer_end, m->d.L, obj);
         if (m->unfused || m->engine)
-            return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u runs the %s path; a batch takes models of the fused five-launch path", fn, i,
-                        m->unfused ? "1:1 (NFAI_LLAMA_UNFUSED)" : "engine");
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: %s runs the %s path; a %s takes models of the fused five-launch path", fn, who,
+                        m->unfused ? "1:1 (NFAI_LLAMA_UNFUSED)" : "engine", obj);
         if (m->kv_f16 != m0->kv_f16)
-            return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u keeps an %s KV cache, member 0 an %s one; one element type per batch", fn, i,
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: %s keeps an %s KV cache, member 0 an %s one; one element type per batch", fn, who,
                         m->kv_f16 ? "fp16" : "fp32", m0->kv_f16 ? "fp16" : "fp32");
         // matrix types: fp16 throughout, or (NFAI_BATCH_QUANT) Q4_K / Q6_K in the T16 layout throughout, in any per-tensor mix
         const bool allow_q = (flags & NFAI_BATCH_QUANT) != 0;
@@ -2243,14 +2279,14 @@ static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t fl
                 return NFAI_OK;
             }
             if (!allow_q)
-                return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u: %s of block %zu has ggml type %d; the batched kernels take fp16 matrices "
-                                                  "(K-quant and Q8_0 weights decode through nfai_hip_llama_decode_step)", fn, i, what, blk, ggml_type_of(t.type));
+                return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu has ggml type %d; the batched kernels take fp16 matrices "
+                                                  "(K-quant and Q8_0 weights decode through nfai_hip_llama_decode_step)", fn, who, what, blk, ggml_type_of(t.type));
             if (t.type == NFAI_Q4_K || t.type == NFAI_Q6_K)
-                return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u: %s of block %zu (ggml type %d, %llu rows) runs the VALU fallback (rows %% 16 != 0); the batched "
-                                                  "int8-MFMA kernels take 16-row tiles", fn, i, what, blk, ggml_type_of(t.type), (unsigned long long)t.rows);
+                return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu (ggml type %d, %llu rows) runs the VALU fallback (rows %% 16 != 0); the batched "
+                                                  "int8-MFMA kernels take 16-row tiles", fn, who, what, blk, ggml_type_of(t.type), (unsigned long long)t.rows);
             if (t.type != NFAI_Q4_K_T16 && t.type != NFAI_Q6_K_T16)
-                return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u: %s of block %zu has ggml type %d; a quantised batch takes Q4_K and Q6_K matrices "
-                                                  "(Q5_K and Q8_0 weights decode through nfai_hip_llama_decode_step)", fn, i, what, blk, ggml_type_of(t.type));
+                return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu has ggml type %d; a quantised %s takes Q4_K and Q6_K matrices "
+                                                  "(Q5_K and Q8_0 weights decode through nfai_hip_llama_decode_step)", fn, who, what, blk, ggml_type_of(t.type), obj);
             if (!firstq) { firstq = what; firstq_blk = blk; firstq_type = ggml_type_of(t.type); }
             return NFAI_OK;
         };
@@ -2262,8 +2298,8 @@ static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t fl
             S_TRY(mat(L.wgate, "ffn_gate", l)); S_TRY(mat(L.wup, "ffn_up", l)); S_TRY(mat(L.wdown, "ffn_down", l));
         }
         if (first16 && firstq)
-            return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u mixes fp16 and quantised matrices (%s of block %zu is fp16, %s of block %zu has ggml type %d); "
-                                              "a batch runs one kernel family", fn, i, first16, first16_blk, firstq, firstq_blk, firstq_type);
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: %s mixes fp16 and quantised matrices (%s of block %zu is fp16, %s of block %zu has ggml type %d); "
+                                              "a %s runs one kernel family", fn, who, first16, first16_blk, firstq, firstq_blk, firstq_type, obj);
         quant = firstq != nullptr;   // (every member reads member 0's tensors, checked below)
         // the same tensors as member 0: a donor and models that called nfai_hip_llama_share_tensors on it, in any order
         bool same = m->layers.size() == m0->layers.size() && m->token_embd.ptr == m0->token_embd.ptr && m->output.ptr == m0->output.ptr &&
@@ -2276,39 +2312,54 @@ static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t fl
                    A.ffn_norm.ptr == B.ffn_norm.ptr && A.wgate.ptr == B.wgate.ptr && A.wup.ptr == B.wup.ptr && A.wdown.ptr == B.wdown.ptr;
         }
         if (!same)
-            return fail(NFAI_ERR_UNSUPPORTED, "%s: member %u does not read the same tensors as member 0 (one copy of the weights per batch: "
-                                              "nfai_hip_llama_share_tensors)", fn, i);
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: %s does not read the same tensors as member 0 (one copy of the weights per batch: "
+                                              "nfai_hip_llama_share_tensors)", fn, who);
     }
     if (!m0->token_embd.ptr) return fail(NFAI_ERR_UNSUPPORTED, "%s: member 0 has no token embedding", fn);
     Batch *bt = new Batch();
     bt->ctx = m0->ctx;
     bt->n = n;
     bt->quant = quant;
-    for (uint32_t i = 0; i < n; i++) { bt->handles[i] = models[i]; bt->mem[i] = mem[i]; bt->serial[i] = mem[i]->serial; bt->gen[i] = mem[i]->weights_gen; }
+    for (uint32_t i = 0; i < n; i++) {
+        Model *m = mem[i];
+        bt->handles[i] = models[i]; bt->mem[i] = m; bt->serial[i] = m->serial; bt->gen[i] = m->weights_gen;
+        bt->cx[i] = m->x; bt->ch[i] = m->h; bt->cq[i] = m->q; bt->catt[i] = m->att; bt->cact[i] = m->act; bt->clog[i] = m->logits;
+    }
+    if (win_tokens) {
+        bt->magic = WIN_MAGIC; bt->window = true; bt->max_tokens = win_tokens;
+        for (uint32_t i = 0; i < BATCH_MAX; i++) { bt->handles[i] = models[0]; bt->mem[i] = m0; bt->serial[i] = m0->serial; bt->gen[i] = m0->weights_gen; }
+    }
     // shapes the batched kernels take (nothing is allocated before this is known)
     {
         BatchOps ops{bt};
         uint32_t dummy = 0;
         bt->d_tok = &dummy; bt->d_am = &dummy; bt->d_attn = &dummy;   // placeholders for the argument checks only
         bool ok = attn_group_ok(m0->d.H / m0->d.Hkv);
-        if (quant) {   // per block: the types, and with them the q|k|v split and the LDS of a launch, differ from block to block
-            for (size_t l = 0; ok && l < m0->layers.size(); l++) {
-                const Layer &L = m0->layers[l];
-                BatchKqArgs qkv[2];
-                const int nq = batch_qkv_kq(ops, l, qkv);
-                for (int j = 0; j < nq; j++) ok = ok && batch_gemv_kq_ok(qkv[j]);
-                ok = ok && L.wgate.type == L.wup.type && batch_gemv_kq_ok(batch_kq(ops.wo(l), L.wo.type)) &&
-                     batch_gemv_kq_ok(batch_kq(ops.gateup(l), L.wgate.type)) && batch_gemv_kq_ok(batch_kq(ops.down(l), L.wdown.type));
+        uint32_t t_bad = n;   // the column count the kernels refuse (a window is checked at every count it may be called with)
+        for (uint32_t t = win_tokens ? 1 : n; ok && t <= (win_tokens ? win_tokens : n); t++) {
+            bt->n = t_bad = t;
+            if (quant) {   // per block: the types, and with them the q|k|v split and the LDS of a launch, differ from block to block
+                for (size_t l = 0; ok && l < m0->layers.size(); l++) {
+                    const Layer &L = m0->layers[l];
+                    BatchKqArgs qkv[2];
+                    const int nq = batch_qkv_kq(ops, l, qkv);
+                    for (int j = 0; j < nq; j++) ok = ok && batch_gemv_kq_ok(qkv[j]);
+                    ok = ok && L.wgate.type == L.wup.type && batch_gemv_kq_ok(batch_kq(ops.wo(l), L.wo.type)) &&
+                         batch_gemv_kq_ok(batch_kq(ops.gateup(l), L.wgate.type)) && batch_gemv_kq_ok(batch_kq(ops.down(l), L.wdown.type));
+                }
+                ok = ok && m0->d.E % 256 == 0 && batch_gemv_kq_ok(batch_kq(ops.head(), (m0->output.ptr ? m0->output : m0->token_embd).type));
+            } else {
+                ok = ok && batch_gemv_ok(ops.qkv(0)) && batch_gemv_ok(ops.wo(0)) && batch_gemv_ok(ops.gateup(0)) && batch_gemv_ok(ops.down(0)) &&
+                     batch_gemv_ok(ops.head());
             }
-            ok = ok && m0->d.E % 256 == 0 && batch_gemv_kq_ok(batch_kq(ops.head(), (m0->output.ptr ? m0->output : m0->token_embd).type));
-        } else {
-            ok = ok && batch_gemv_ok(ops.qkv(0)) && batch_gemv_ok(ops.wo(0)) && batch_gemv_ok(ops.gateup(0)) && batch_gemv_ok(ops.down(0)) &&
-                 batch_gemv_ok(ops.head());
         }
         bt->d_tok = nullptr; bt->d_am = nullptr; bt->d_attn = nullptr;
         if (!ok) {
             const nfai_llama_desc &d = m0->d;
             delete bt;
+            if (win_tokens)
+                return fail(NFAI_ERR_UNSUPPORTED, "%s: the batched kernels do not take this shape at %u of the window's %u columns (E %u, F %u, H %u, "
+                                                  "Hkv %u, D %u, V %u)", fn, t_bad, win_tokens, d.E, d.F, d.H, d.Hkv, d.D, d.V);
             return fail(NFAI_ERR_UNSUPPORTED, "%s: the batched kernels do not take this shape at n = %u (E %u, F %u, H %u, Hkv %u, D %u, V %u)", fn, n,
                         d.E, d.F, d.H, d.Hkv, d.D, d.V);
         }
@@ -2317,9 +2368,22 @@ static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t fl
     int rc;
     if ((rc = dalloc(reinterpret_cast<void **>(&bt->d_tok), 256, bt->ctx->stream))) return bail(rc);
     if ((rc = dalloc(&bt->d_am, batch_argmax_bytes(), bt->ctx->stream))) return bail(rc);
-    if ((rc = dalloc(&bt->d_attn, batch_attn_bytes(m0->d.H, m0->d.D), bt->ctx->stream))) return bail(rc);
+    if ((rc = dalloc(&bt->d_attn, win_tokens ? window_attn_bytes(m0->d.H, m0->d.D) : batch_attn_bytes(m0->d.H, m0->d.D), bt->ctx->stream))) return bail(rc);
+    if (win_tokens) {   // the columns' own activation vectors (the model's stay what its last own token left)
+        const nfai_llama_desc &d = m0->d;
+        auto r64 = [](size_t v) { return (v + 63) & ~(size_t)63; };   // every vector on a 256-byte boundary
+        const size_t E = r64(d.E), HD = r64((size_t)d.H * d.D), F = r64(d.F), per = 2 * E + 2 * HD + F + r64(d.V);
+        if ((rc = dalloc(reinterpret_cast<void **>(&bt->w_act), per * win_tokens * 4, bt->ctx->stream))) return bail(rc);
+        bt->w_act_floats = per * win_tokens;
+        for (uint32_t i = 0; i < win_tokens; i++) {
+            float *b = bt->w_act + per * i;
+            bt->cx[i] = b; bt->ch[i] = b + E; bt->cq[i] = b + 2 * E; bt->catt[i] = b + 2 * E + HD; bt->cact[i] = b + 2 * E + 2 * HD;
+            bt->clog[i] = b + 2 * E + 2 * HD + F;
+        }
+    }
     if (hipHostMalloc(reinterpret_cast<void **>(&bt->h_pin), 256, hipHostMallocDefault) != hipSuccess) return bail(fail(NFAI_ERR_OOM, "%s: pinned staging", fn));
     memset(bt->h_pin, 0, 256);
+    bt->d_in = win_tokens ? bt->d_tok + WIN_IN : bt->d_tok;
     if (hipStreamSynchronize(bt->ctx->stream) != hipSuccess) return bail(fail(NFAI_ERR_HIP, "%s: stream synchronisation failed", fn));
     handle_register(bt);
     *out = reinterpret_cast<nfai_batch_t>(bt);
@@ -2466,5 +2530,228 @@ NFAI_API int32_t nfai_hip_llama_batch_profile_step(nfai_batch_t h, const uint32_
     const uint32_t code = bt->h_pin[16 + BATCH_MAX];
     if (code) return batch_device_failed(bt, code, "batch_profile_step");
     for (uint32_t i = 0; i < bt->n; i++) { bt->mem[i]->pos_host++; bt->mem[i]->x_last = bt->mem[i]->x; }
+    return NFAI_OK;
+}
+
+// ---- window: up to 8 CONSECUTIVE positions of one sequence per pass over the weights (greedy speculative decoding) ------------------
+// The batched launches with every column bound to the same model at positions p, p + 1, ... (BatchGemvArgs::pos_off), the window
+// attention (kernels_attn_window.hip) in place of k_battn, and the accept rule in the lm_head tail (win_tail, common.h).  A window
+// is a Batch with `window` set: it owns the columns' activation vectors, workspaces, token / draft / result words, pinned staging
+// and one graph per column count; the weights, the KV cache, the position word, the token word and the ring are the model's.
+namespace {
+
+Batch *window_of(nfai_window_t h)
+{
+    if (!handle_live(h)) return nullptr;
+    Batch *b = reinterpret_cast<Batch *>(h);
+    return b->magic == WIN_MAGIC ? b : nullptr;
+}
+
+#define WINDOW_OR_FAIL(bt, h)                                                      \
+    Batch *bt = window_of(h);                                                      \
+    if (!bt) return fail(NFAI_ERR_INVALID, "%s: invalid window handle", __func__); \
+    HIP_TRY(hipSetDevice(bt->ctx->device))
+
+// the window's model is still the one it was created over (the serial + generation check of batch_members_live)
+int window_model_live(Batch *bt, const char *fn)
+{
+    Model *m = model_of(bt->handles[0]);
+    if (!m || m != bt->mem[0] || m->serial != bt->serial[0])
+        return fail(NFAI_ERR_INVALID, "%s: invalid window: its model was destroyed while the window held it", fn);
+    if (!m->finalized || m->weights_gen != bt->gen[0])
+        return fail(NFAI_ERR_INVALID, "%s: invalid window: the model's tensors changed after the window was created (make a new window)", fn);
+    return NFAI_OK;
+}
+
+// token words, drafts and their count H2D from pinned memory -> the step -> ArgMax words, error word and emitted count D2H
+int window_capture(Batch *bt, uint32_t t)
+{
+    if (bt->wx[t]) return NFAI_OK;
+    hipStream_t s = bt->ctx->stream;
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = NFAI_OK;
+    hipError_t e = hipMemcpyAsync(bt->d_tok + WIN_IN, bt->h_pin, (2 * BATCH_MAX + 1) * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) rc = enqueue_batch(bt);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(bt->h_pin + WIN_IN, bt->d_tok, (BATCH_MAX + 2) * 4, hipMemcpyDeviceToHost, s);
+    hipGraph_t cg = nullptr;
+    const hipError_t e2 = hipStreamEndCapture(s, &cg);   // a stream left in capture mode would poison every later call
+    if (rc || e != hipSuccess || e2 != hipSuccess) {
+        if (cg) hipGraphDestroy(cg);
+        if (rc) return rc;
+        return fail(NFAI_ERR_HIP, "capturing the window graph failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    }
+    bt->wg[t] = cg;
+    HIP_TRY(hipGraphInstantiate(&bt->wx[t], cg, nullptr, nullptr, 0));
+    return NFAI_OK;
+}
+
+// The arguments every stepping entry point checks before anything is enqueued; sets the column count and fills the pinned words.
+// k = WIN_ALL: a multi-token step (every column is kept).
+int window_prepare(Batch *bt, const uint32_t *tokens, uint32_t t, const uint32_t *draft, uint32_t k, const char *fn)
+{
+    int rc;
+    if ((rc = window_model_live(bt, fn))) return rc;
+    Model *m = bt->mem[0];
+    if (t < 1 || t > bt->max_tokens) return fail(NFAI_ERR_INVALID, "%s: invalid token count %u (this window takes 1 to %u per step)", fn, t, bt->max_tokens);
+    for (uint32_t i = 0; i < t; i++)
+        if (tokens[i] >= m->d.V) return fail(NFAI_ERR_INVALID, "%s: column %u: token %u >= vocab %u", fn, i, tokens[i], m->d.V);
+    if ((uint64_t)m->pos_host + t > m->d.C)
+        return fail(NFAI_ERR_KV_FULL, "%s: KV cache full: %u position(s) from position %u exceed capacity %u (the reference would write out of "
+                                      "bounds here)", fn, t, m->pos_host, m->d.C);
+    bt->n = t;
+    for (uint32_t i = 0; i < BATCH_MAX; i++) {
+        bt->h_pin[i] = i < t ? tokens[i] : 0u;
+        bt->h_pin[BATCH_MAX + i] = (k != WIN_ALL && i < k) ? draft[i] : 0u;
+    }
+    bt->h_pin[2 * BATCH_MAX] = k;
+    return NFAI_OK;
+}
+
+// After the synchronisation: the device-side bound (a position word at or past the capacity: nothing was written, the error word is
+// set) or the emitted count; the host's view of the position follows the device's.
+int window_finish(Batch *bt, uint32_t *n_out, const char *fn)
+{
+    Model *m = bt->mem[0];
+    hipStream_t s = bt->ctx->stream;
+    const uint32_t code = bt->h_pin[WIN_IN + BATCH_MAX];
+    if (code) {
+        HIP_TRY(hipMemcpyAsync(m->d_pos, &m->pos_host, 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(bt->d_tok + BATCH_MAX, 0, 4, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        bt->h_pin[WIN_IN + BATCH_MAX] = 0;
+        return fail(NFAI_ERR_KV_FULL, "%s: column %u: the position word on the device put it at or past the KV capacity %u (code 0x%x); the "
+                                      "position did not move", fn, code & 0xFFu, m->d.C, code);
+    }
+    const uint32_t n = bt->h_pin[WIN_IN + WIN_NOUT];
+    if (n < 1 || n > bt->n) return fail(NFAI_ERR_HIP, "%s: the device reported %u emitted tokens of %u columns", fn, n, bt->n);
+    m->pos_host += n;
+    m->x_last = bt->cx[n - 1];
+    *n_out = n;
+    return NFAI_OK;
+}
+
+int window_run(Batch *bt, float *logits_host, uint32_t *n_out, const char *fn)
+{
+    int rc;
+    if ((rc = window_capture(bt, bt->n))) return rc;
+    hipStream_t s = bt->ctx->stream;
+    HIP_TRY(hipGraphLaunch(bt->wx[bt->n], s));
+    if (logits_host) {   // the columns' logits behind the graph, in front of the ONE synchronisation
+        const size_t V = bt->mem[0]->d.V;
+        for (uint32_t i = 0; i < bt->n; i++) HIP_TRY(hipMemcpyAsync(logits_host + i * V, bt->clog[i], V * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return window_finish(bt, n_out, fn);
+}
+
+}  // namespace
+
+NFAI_API int32_t nfai_hip_llama_window_create(nfai_model_t model, uint32_t max_tokens, uint32_t flags, nfai_window_t *out)
+{
+    if (!out) return fail(NFAI_ERR_INVALID, "window_create: null argument");
+    if (max_tokens < 2 || max_tokens > BATCH_MAX)
+        return fail(NFAI_ERR_INVALID, "window_create: invalid max_tokens = %u (a window takes 2 to %u tokens per step)", max_tokens, BATCH_MAX);
+    return batch_create_impl(&model, 1, flags, out, "window_create", max_tokens);
+}
+
+NFAI_API int32_t nfai_hip_llama_window_destroy(nfai_window_t h)
+{
+    WINDOW_OR_FAIL(bt, h);
+    hipStreamSynchronize(bt->ctx->stream);
+    Model *m = model_of(bt->handles[0]);
+    // the hidden state of the last token is where that token left it (window_finish); a model whose last token went through THIS
+    // window falls back to its own vector, one that went through another window or its own path since keeps what it has
+    if (m && m == bt->mem[0] && m->serial == bt->serial[0] && bt->w_act && m->x_last >= bt->w_act && m->x_last < bt->w_act + bt->w_act_floats)
+        m->x_last = m->x;
+    handle_unregister(bt);
+    batch_free(bt);
+    return NFAI_OK;
+}
+
+NFAI_API int32_t nfai_hip_llama_window_step(nfai_window_t h, const uint32_t *tokens, uint32_t t, float *logits_host, uint32_t *argmax)
+{
+    WINDOW_OR_FAIL(bt, h);
+    if (!tokens) return fail(NFAI_ERR_INVALID, "window_step: null tokens");
+    int rc;
+    if ((rc = window_prepare(bt, tokens, t, nullptr, WIN_ALL, "window_step"))) return rc;
+    uint32_t n = 0;
+    if ((rc = window_run(bt, logits_host, &n, "window_step"))) return rc;
+    if (argmax)
+        for (uint32_t i = 0; i < t; i++) argmax[i] = bt->h_pin[WIN_IN + i];
+    return NFAI_OK;
+}
+
+NFAI_API int32_t nfai_hip_llama_window_verify(nfai_window_t h, uint32_t token, const uint32_t *draft, uint32_t k, float *logits_host,
+                                              uint32_t *tokens_out, uint32_t *n_out)
+{
+    WINDOW_OR_FAIL(bt, h);
+    if (!tokens_out || !n_out || (k && !draft)) return fail(NFAI_ERR_INVALID, "window_verify: null argument");
+    if (k + 1 > bt->max_tokens || k >= BATCH_MAX)
+        return fail(NFAI_ERR_INVALID, "window_verify: invalid draft count %u (this window verifies 0 to %u drafts per step)", k, bt->max_tokens - 1);
+    uint32_t cols[BATCH_MAX] = {token};
+    for (uint32_t i = 0; i < k; i++) cols[1 + i] = draft[i];
+    int rc;
+    if ((rc = window_prepare(bt, cols, k + 1, draft, k, "window_verify"))) return rc;
+    uint32_t n = 0;
+    if ((rc = window_run(bt, logits_host, &n, "window_verify"))) return rc;
+    for (uint32_t i = 0; i < n; i++) tokens_out[i] = bt->h_pin[WIN_IN + i];
+    *n_out = n;
+    return NFAI_OK;
+}
+
+NFAI_API int32_t nfai_hip_llama_window_bytes_per_step(nfai_window_t h, uint32_t t, uint64_t *total)
+{
+    WINDOW_OR_FAIL(bt, h);
+    int rc;
+    if ((rc = window_model_live(bt, "window_bytes_per_step"))) return rc;
+    if (t < 1 || t > bt->max_tokens) return fail(NFAI_ERR_INVALID, "window_bytes_per_step: invalid token count %u (1 to %u)", t, bt->max_tokens);
+    Model *m = bt->mem[0];
+    const nfai_llama_desc &d = m->d;
+    uint64_t b = 0;
+    for (const Layer &L : m->layers)   // every weight byte once per step, as a batch step (nfai_hip_llama_batch_bytes_per_token)
+        b += tensor_bytes(L.wq) + tensor_bytes(L.wk) + tensor_bytes(L.wv) + tensor_bytes(L.wo) + tensor_bytes(L.wgate) + tensor_bytes(L.wup) + tensor_bytes(L.wdown);
+    b += tensor_bytes(m->output.ptr ? m->output : m->token_embd);
+    if (bt->quant) {
+        for (const Layer &L : m->layers) b += tensor_bytes(L.attn_norm) + tensor_bytes(L.ffn_norm);
+        b += tensor_bytes(m->output_norm);
+    }
+    if (!bt->quant || m->output.ptr) b += (uint64_t)t * weight_row_bytes(m->token_embd.type, d.E);
+    // KV: the p prefix rows ONCE for all columns, column i's i + 1 window rows, t rows written
+    const uint64_t row = 2ull * d.Hkv * d.D * m->kv_esz;
+    b += (uint64_t)m->layers.size() * row * ((uint64_t)m->pos_host + (uint64_t)t * (t + 1) / 2 + t);
+    if (total) *total = b;
+    return NFAI_OK;
+}
+
+// One window step of t tokens (as _window_step without results: the position advances by t) launch by launch between hipEvents.
+NFAI_API int32_t nfai_hip_llama_window_profile_step(nfai_window_t h, const uint32_t *tokens, uint32_t t, float *ms_by_class, uint32_t *launches_by_class)
+{
+    WINDOW_OR_FAIL(bt, h);
+    if (!tokens || !ms_by_class || !launches_by_class) return fail(NFAI_ERR_INVALID, "window_profile_step: null argument");
+    int rc;
+    if ((rc = window_prepare(bt, tokens, t, nullptr, WIN_ALL, "window_profile_step"))) return rc;
+    hipStream_t s = bt->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(bt->d_tok + WIN_IN, bt->h_pin, (2 * BATCH_MAX + 1) * 4, hipMemcpyHostToDevice, s));
+    for (int c = 0; c < KC_N; c++) { ms_by_class[c] = 0.f; launches_by_class[c] = 0; }
+    if ((rc = enqueue_batch(bt, ms_by_class, launches_by_class))) return rc;
+    HIP_TRY(hipMemcpyAsync(bt->h_pin + WIN_IN, bt->d_tok, (BATCH_MAX + 2) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    uint32_t n = 0;
+    return window_finish(bt, &n, "window_profile_step");
+}
+
+// Test hook (not in nfai_hip.h, like nfai_hip_debug_read_kv_rows): column `col`'s vector of the last window call — which 1 = q of the
+// last block (after RoPE), 2 = that block's attention output — for tests that check the window attention launch on its own.
+NFAI_API int32_t nfai_hip_debug_window_read(nfai_window_t h, uint32_t col, int32_t which, float *host, uint64_t n)
+{
+    WINDOW_OR_FAIL(bt, h);
+    int rc;
+    if ((rc = window_model_live(bt, "debug_window_read"))) return rc;
+    Model *m = bt->mem[0];
+    if (!host || col >= bt->max_tokens || (which != 1 && which != 2) || n > (uint64_t)m->d.H * m->d.D)
+        return fail(NFAI_ERR_INVALID, "debug_window_read: invalid argument");
+    HIP_TRY(hipMemcpyAsync(host, which == 1 ? bt->cq[col] : bt->catt[col], n * 4, hipMemcpyDeviceToHost, bt->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(bt->ctx->stream));
     return NFAI_OK;
 }

@@ -155,6 +155,8 @@ class LlamaModel:
         call("nfai_hip_llama_create", mgr.handle, C.byref(desc), C.byref(h))
         self.handle = h
         self._keep = []
+        self._quantized = bool(getattr(share_from, "_quantized", False))   # any matrix in a block encoding (picks the window's kernel family)
+        self._windows = {}
         if share_from is not None:  # another slot of the same pipeline stage: the donor's weights, no copy, no second repack
             self._donor = share_from
             call("nfai_hip_llama_share_tensors", self.handle, share_from.handle)
@@ -166,9 +168,12 @@ class LlamaModel:
     def SetTensor(self, name: str, t) -> None:
         if isinstance(t, tuple):  # already resident in HBM
             ptr, ty, rows, cols = t
+            if rows > 1 and ty not in (_lib.F32, _lib.F16):
+                self._quantized = True
             call("nfai_hip_llama_set_tensor_device", self.handle, name.encode(), ty, rows, cols, C.c_void_p(ptr))
             return
         if isinstance(t, QuantTensor):
+            self._quantized = True
             a, ty, (rows, cols) = np.ascontiguousarray(t.data), t.ggml_type, t.shape
         else:
             a = np.ascontiguousarray(t)
@@ -290,7 +295,58 @@ class LlamaModel:
         return us.value
 
     # -- the token loop (LlamaModel.RunAsync, :99-174)
-    def RunAsync(self, prompt: str, greedy: bool = False, max_tokens: int | None = None, rng=None):
+    def RunAsync(self, prompt: str, greedy: bool = False, max_tokens: int | None = None, rng=None, speculative: int = 0, drafter=None):
+        """speculative = k > 0 (greedy only): every pass over the weights verifies up to k tokens guessed by `drafter` (default:
+        PromptLookupDrafter, an n-gram lookup in the conversation so far) through a LlamaWindow; the tokens are exactly those of the
+        plain greedy loop.  0 (the default) is that plain loop."""
+        speculative = int(speculative)
+        if speculative < 0 or speculative > 7:
+            raise ValueError(f"RunAsync: speculative = {speculative} outside [0, 7]")
+        if speculative and not greedy:
+            raise ValueError("RunAsync: speculative decoding verifies drafts against ArgMax; it needs greedy=True "
+                             "(speculative sampling for TopP is not implemented)")
+        if speculative:
+            return self._run_speculative(prompt, max_tokens, speculative, drafter)
+        return self._run(prompt, greedy, max_tokens, rng)
+
+    def _run_speculative(self, prompt: str, max_tokens, k: int, drafter):
+        if self.tokenizer is None:
+            raise RuntimeError("RunAsync needs a tokenizer (nfai_amd.tokenizer.Tokenizer(metadata))")
+        from .drafter import PromptLookupDrafter
+        drafter = drafter if drafter is not None else PromptLookupDrafter()
+        tokenIds = [int(t) for t in self.tokenizer.Tokenize(prompt, addBos=self.firstInput)]
+        self.firstInput = False
+        win = self._windows.get(k + 1)
+        if win is None:
+            win = self._windows[k + 1] = LlamaWindow(self, k + 1, quantized=self._quantized)
+        if self.promptPrefill:
+            self.Ingest(tokenIds[:-1])
+        else:
+            for tok in tokenIds[:-1]:
+                self.Step(tok, want_logits=False)
+        eos = self.tokenizer.EosTokenId
+        history = list(tokenIds)   # every token the model has been fed or has emitted; history[-1] is the one to feed next
+        n = 0
+        while n == 0 or max_tokens is None or n < max_tokens:
+            room = self.C - self.Pos - 1   # drafts the cache still holds behind the token itself
+            budget = k if max_tokens is None else min(k, max_tokens - n - 1)
+            draft = [int(t) for t in drafter.Propose(history, max(0, min(budget, room)))]
+            # the plain loop never feeds an emitted EOS: it stops with the position in front of it.  A draft that held EOS and was
+            # accepted would put EOS, and whatever was guessed behind it, into the KV cache for the next turn to continue from.
+            if eos in draft:
+                draft = draft[:draft.index(eos)]
+            out = win.Verify(history[-1], draft, want_logits=False)[1]
+            for tk in out:
+                tk = int(tk)
+                n += 1
+                if tk == eos and n > 1:
+                    return
+                yield self.tokenizer.Detokenize([tk])   # (the first token is yielded whatever it is, as the plain loop does)
+                if tk == eos:
+                    return
+                history.append(tk)
+
+    def _run(self, prompt: str, greedy: bool, max_tokens, rng):
         if self.tokenizer is None:
             raise RuntimeError("RunAsync needs a tokenizer (nfai_amd.tokenizer.Tokenizer(metadata))")
         tokenIds = self.tokenizer.Tokenize(prompt, addBos=self.firstInput)
@@ -322,6 +378,9 @@ class LlamaModel:
 
     def Dispose(self) -> None:  # the reference throws NotImplementedException (:70-74)
         if self.handle is not None:
+            for w in self._windows.values():
+                w.Dispose()
+            self._windows = {}
             call("nfai_hip_llama_destroy", self.handle)
             self.handle = None
 
@@ -386,6 +445,62 @@ class LlamaBatch:
     def Dispose(self) -> None:
         if self.handle is not None:
             call("nfai_hip_llama_batch_destroy", self.handle)
+            self.handle = None
+
+
+class LlamaWindow:
+    """Up to `max_tokens` (2..8) CONSECUTIVE positions of ONE LlamaModel per pass over the weights (nfai_hip_llama_window_*): what
+    max_tokens passes of the token loop (LlamaModel.cs:116-125) do, with every weight row and every cached K / V row read once.
+    `Verify` is lossless greedy speculative decoding: guessed tokens ride as extra columns and are kept as far as the model's own
+    ArgMax agrees.  The model stays a normal LlamaModel between window calls."""
+
+    def __init__(self, model, max_tokens: int, quantized: bool = False):
+        self.model = model
+        self.max_tokens = int(max_tokens)
+        self.V = int(model.dims["V"])
+        h = _lib.H()
+        call("nfai_hip_llama_window_create", model.handle, self.max_tokens, _lib.BATCH_QUANT if quantized else 0, C.byref(h))
+        self.handle = h
+
+    def Step(self, tokens, want_logits: bool = True):
+        """tokens[i] at position p + i: (logits[t][V] | None, argmax[t]); the position advances by t."""
+        t = np.ascontiguousarray(tokens, np.uint32)
+        logits = np.empty((t.size, self.V), np.float32) if want_logits else None
+        am = np.empty(t.size, np.uint32)
+        call("nfai_hip_llama_window_step", self.handle, t.ctypes.data_as(C.POINTER(C.c_uint32)), t.size,
+             logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None, am.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return logits, am
+
+    def Verify(self, token: int, draft=(), want_logits: bool = False):
+        """`token` and the k guessed tokens behind it in one pass: (logits[k + 1][V] | None, emitted tokens).  The emitted tokens
+        (1 to k + 1 of them) are exactly what that many plain greedy steps from `token` would return."""
+        d = np.ascontiguousarray(draft, np.uint32).reshape(-1)
+        k = int(d.size)
+        logits = np.empty((k + 1, self.V), np.float32) if want_logits else None
+        out = np.empty(k + 1, np.uint32)
+        n = C.c_uint32()
+        call("nfai_hip_llama_window_verify", self.handle, int(token), d.ctypes.data_as(C.POINTER(C.c_uint32)) if k else None, k,
+             logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None, out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n))
+        return logits, out[:n.value].copy()
+
+    def BytesPerStep(self, t: int) -> int:
+        """Algorithmic HBM bytes of one window step of t tokens at the model's current position."""
+        b = C.c_uint64()
+        call("nfai_hip_llama_window_bytes_per_step", self.handle, int(t), C.byref(b))
+        return b.value
+
+    def ProfileStep(self, tokens):
+        """One window step launch by launch: {class: (ms, launches)}; the position advances by len(tokens)."""
+        t = np.ascontiguousarray(tokens, np.uint32)
+        ms = (C.c_float * 8)()
+        n = (C.c_uint32 * 8)()
+        call("nfai_hip_llama_window_profile_step", self.handle, t.ctypes.data_as(C.POINTER(C.c_uint32)), t.size, ms, n)
+        names = ["qkv", "attn", "wo", "gateup", "down", "lmhead", "other", "engine"]
+        return {k: (ms[i], n[i]) for i, k in enumerate(names)}
+
+    def Dispose(self) -> None:
+        if self.handle is not None:
+            call("nfai_hip_llama_window_destroy", self.handle)
             self.handle = None
 
 
