@@ -16,15 +16,18 @@ public sealed unsafe class HipLlamaBatch : IDisposable
     /// K-quant weights (unless quantized), pipeline stages, mixed KV types, separate weights, duplicates.</summary>
     /// quantized: also admits members whose matrices are all Q4_K / Q6_K (Q4_K_M files) through nfai_hip_llama_batch_create_ex with
     /// NFAI_BATCH_QUANT: every quantised row is read and unpacked once per step and multiplied on the matrix cores for all members.
-    public HipLlamaBatch(ReadOnlySpan<ulong> models, uint vocab, bool quantized = false)
+    /// anyQuant (with quantized): Q5_K and Q8_0 matrices too (Q5_K_M and Q8_0 files, NFAI_BATCH_QUANT_ANY), in any per-tensor mix.
+    public HipLlamaBatch(ReadOnlySpan<ulong> models, uint vocab, bool quantized = false, bool anyQuant = false)
     {
+        if (anyQuant && !quantized) throw new ArgumentException("anyQuant widens quantized and needs it", nameof(anyQuant));
         Count = (uint)models.Length; Vocab = vocab;
         fixed (ulong* p = models)
-            Native.Check(quantized ? Native.nfai_hip_llama_batch_create_ex(p, Count, BatchQuant, out handle)
+            Native.Check(quantized ? Native.nfai_hip_llama_batch_create_ex(p, Count, BatchQuant | (anyQuant ? BatchQuantAny : 0u), out handle)
                                    : Native.nfai_hip_llama_batch_create(p, Count, out handle));
     }
 
     private const uint BatchQuant = 1u;   // NFAI_BATCH_QUANT (nfai_hip.h)
+    private const uint BatchQuantAny = 4u;   // NFAI_BATCH_QUANT_ANY
 
     /// <summary>One token per member (one pass of LlamaModel.cs:116-125 for every sequence): tokens[i] runs at member i's own position
     /// in member i's own cache; argmax[i] is the first index of member i's largest logit (SamplingUtils.cs:55-56).  logits: Count * Vocab

@@ -11,16 +11,19 @@ public sealed unsafe class HipLlamaWindow : IDisposable
     public uint Vocab { get; }
 
     /// <summary>model: a finalized, whole model of the fused path (HipLlamaModel.Handle); maxTokens in [2, 8].  quantized: its matrices
-    /// are all Q4_K / Q6_K (Q4_K_M files, NFAI_BATCH_QUANT) instead of all fp16.  The window owns the columns' activation vectors, its
+    /// are all Q4_K / Q6_K (Q4_K_M files, NFAI_BATCH_QUANT) instead of all fp16; anyQuant (with quantized): Q5_K and
+    /// Q8_0 matrices too (Q5_K_M and Q8_0 files, NFAI_BATCH_QUANT_ANY).  The window owns the columns' activation vectors, its
     /// workspaces and graphs, no weights and no KV cache; the model stays a normal model between window calls.  Throws with tensor and
-    /// type for Q5_K / Q8_0 weights, pipeline stages, the 1:1 or engine path.</summary>
-    public HipLlamaWindow(ulong model, uint maxTokens, uint vocab, bool quantized = false)
+    /// type for Q5_K / Q8_0 weights without anyQuant, pipeline stages, the 1:1 or engine path.</summary>
+    public HipLlamaWindow(ulong model, uint maxTokens, uint vocab, bool quantized = false, bool anyQuant = false)
     {
+        if (anyQuant && !quantized) throw new ArgumentException("anyQuant widens quantized and needs it", nameof(anyQuant));
         MaxTokens = maxTokens; Vocab = vocab;
-        Native.Check(Native.nfai_hip_llama_window_create(model, maxTokens, quantized ? BatchQuant : 0u, out handle));
+        Native.Check(Native.nfai_hip_llama_window_create(model, maxTokens, (quantized ? BatchQuant : 0u) | (anyQuant ? BatchQuantAny : 0u), out handle));
     }
 
     private const uint BatchQuant = 1u;   // NFAI_BATCH_QUANT (nfai_hip.h)
+    private const uint BatchQuantAny = 4u;   // NFAI_BATCH_QUANT_ANY
 
     /// <summary>tokens[i] at position p + i (tokens.Length passes of LlamaModel.cs:116-125 on the caller's tokens): argmax[i] is the first
     /// index of column i's largest logit (SamplingUtils.cs:55-56); logits is [tokens.Length][Vocab] or empty.  The position advances

@@ -366,13 +366,19 @@ int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_t n, nfai
  * admits members whose matrices (token_embd and output included) are all Q4_K or Q6_K in any per-tensor mix, as _set_tensor +
  * _finalize leave them for Q4_K_M files: one step reads every quantised row once, unpacks it once and multiplies it on the matrix
  * cores with the fixed-point activations of all members (kernels_gemv_batch_kqm.hip); a q|k|v whose matrices differ in type runs as
- * two launches.  NFAI_ERR_INVALID: unknown flag bits, and everything _batch_create answers so.  NFAI_ERR_UNSUPPORTED under the flag,
- * naming member, tensor and ggml type: Q5_K / Q8_0 matrices, fp16 and quantised matrices in one model, a quantised matrix whose row
- * count is not a multiple of 16 (the VALU fallback), a shape the kernels' LDS plan does not hold, and every refusal of _batch_create.
+ * two launches.  NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY also admits Q5_K and Q8_0 matrices (Q5_K_M and Q8_0 files), in any
+ * per-tensor mix of the four types; a q|k|v then runs as one launch per type present, three at the most.  NFAI_ERR_INVALID: unknown
+ * flag bits, NFAI_BATCH_QUANT_ANY without NFAI_BATCH_QUANT, and everything _batch_create answers so.  Bit 1 is reserved and stays an
+ * unknown bit: flags 2 and 3 have always been answered NFAI_ERR_INVALID, and callers may rely on that answer, so no meaning is given
+ * to it.  NFAI_ERR_UNSUPPORTED under the flag(s), naming member, tensor and ggml type: Q5_K / Q8_0 matrices without
+ * NFAI_BATCH_QUANT_ANY, fp16 and quantised matrices in one model, a quantised matrix whose row count is not a multiple of 16 (the
+ * VALU fallback), a shape the kernels' LDS plan does not hold, and every refusal of _batch_create.
  * The handle works with _batch_step, _batch_greedy, _batch_bytes_per_token (quantised bytes: every T16 plane and norm gain once, an
  * embedding row per member where the table is not the head's, each member's KV rows), _batch_profile_step and _batch_destroy. */
 enum nfai_batch_flags {
-    NFAI_BATCH_QUANT = 1u << 0,   /* admit members whose matrices are all Q4_K / Q6_K */
+    NFAI_BATCH_QUANT     = 1u << 0,   /* admit members whose matrices are all Q4_K / Q6_K */
+    /* 1u << 1 is reserved (see above): it stays an unknown bit */
+    NFAI_BATCH_QUANT_ANY = 1u << 2,   /* with NFAI_BATCH_QUANT: also Q5_K and Q8_0 matrices, any per-tensor mix of the four */
 };
 int32_t nfai_hip_llama_batch_create_ex(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out);
 /* Frees the workspace and the graphs; the members are not touched (≙ leaving the loop LlamaModel.cs:116-125: the models live on). */
@@ -404,10 +410,11 @@ int32_t nfai_hip_llama_batch_profile_step(nfai_batch_t batch, const uint32_t *to
  *      weights, its KV cache (the window attention reads the cached prefix once for all columns, kernels_attn_window.hip), its
  *      position word, token word and ring. ---- */
 /* ≙ preparing to run up to max_tokens passes of the loop LlamaModel.cs:116-125 of ONE LlamaModel at once.  max_tokens in [2, 8].
- * flags: 0 (all matrices NFAI_F16) or NFAI_BATCH_QUANT (all matrices Q4_K / Q6_K).  The model is admitted as _batch_create /
+ * flags: 0 (all matrices NFAI_F16), NFAI_BATCH_QUANT (all matrices Q4_K / Q6_K) or NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY (all
+ * matrices Q4_K / Q5_K / Q6_K / Q8_0).  The model is admitted as _batch_create /
  * _batch_create_ex admit a member, with the same answers: NFAI_ERR_INVALID for a dead handle, max_tokens outside [2, 8], unknown flag
  * bits, a model not finalized; NFAI_ERR_UNSUPPORTED, naming tensor and ggml type, for a pipeline stage, the 1:1 or engine path,
- * Q5_K / Q8_0 matrices, fp16 and quantised matrices in one model, quantised rows % 16 != 0, a shape the kernels' LDS plan does not
+ * Q5_K / Q8_0 matrices without NFAI_BATCH_QUANT_ANY, fp16 and quantised matrices in one model, quantised rows % 16 != 0, a shape the kernels' LDS plan does not
  * hold.  The window owns the columns' activation vectors, workspaces, token / draft / result words, pinned staging and its graphs
  * (one per column count, captured on first use); no weights, no KV cache.  The model stays a normal model: _decode_step, _ingest,
  * _set_pos, _read_kv, _pos between window calls see, and are seen by, the window.  _read: logits are what the model's OWN last token

@@ -339,10 +339,10 @@ size_t window_attn_bytes(uint32_t H, uint32_t D);
 hipError_t launch_window_attn(const WindowAttnArgs &a, hipStream_t s);
 // x[b] = row tok[b] of the fp16 embedding table, widened (TokenEmbedShader.cs:131-159), b < n
 hipError_t launch_batch_embed(const void *table, uint64_t n_rows, uint32_t E, const uint32_t *tok, float *const *x, uint32_t n, hipStream_t s);
-// The same launches on Q4_K / Q6_K matrices in the T16 layout (kernels_gemv_batch_kqm.hip): W[i] are T16 tensors of ONE type (a q|k|v of
-// mixed types is split by type into two launches), seg_role[i] says which of q (0), k (1), v (2) segment i of a q|k|v launch is.
+// The same launches on Q4_K / Q5_K / Q6_K / Q8_0 matrices in the T16 layout (kernels_gemv_batch_kqm.hip): W[i] are T16 tensors of ONE
+// type (a q|k|v of mixed types is split by type into up to three launches), seg_role[i] says which of q (0), k (1), v (2) segment i of a q|k|v launch is.
 struct BatchKqArgs : BatchGemvArgs {
-    int w_type = 0;                    // NFAI_Q4_K_T16 or NFAI_Q6_K_T16
+    int w_type = 0;                    // a T16 type (is_t16)
     uint32_t seg_role[3] = {0, 1, 2};
 };
 bool batch_gemv_kq_ok(const BatchKqArgs &a);   // shape and LDS rules of launch_batch_gemv_kq (checked by nfai_hip_llama_batch_create_ex)

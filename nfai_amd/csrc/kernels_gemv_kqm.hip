@@ -543,7 +543,7 @@ hipError_t launch_embed_kqt(const void *table, int type, uint64_t n_rows, const 
 hipError_t launch_batch_embed_kq(const void *table, int type, uint64_t n_rows, uint32_t E, const uint32_t *tok, float *const *x, uint32_t n, hipStream_t s)
 {
     if (!table || !tok || n < 1 || n > BATCH_MAX || E % 256 || n_rows == 0 || n_rows % 16) return hipErrorInvalidValue;
-    if (type != NFAI_Q4_K_T16 && type != NFAI_Q6_K_T16) return hipErrorInvalidValue;
+    if (!is_t16(type)) return hipErrorInvalidValue;
     EmbedT16Params p{};
     p.table = static_cast<const uint8_t *>(table); p.type = type; p.n_rows = n_rows; p.E = E; p.tok = tok;
     for (uint32_t b = 0; b < n; b++) {

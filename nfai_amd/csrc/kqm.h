@@ -246,7 +246,8 @@ __device__ __forceinline__ float q6t_dot(const Q6T &w, const i32x4 (&af)[4], f32
 }
 
 // ---- a step against several activation vectors (the batched decode): unpack once, then one dot per column ------------------------------
-// The part of q4t_dot / q6t_dot that does not depend on x, done once per step: the four B operands (one byte per weight) and the scales.
+// The part of q4t_dot / q5t_dot / q6t_dot / q8t_dot that does not depend on x, done once per step: the four B operands (one byte per
+// weight) and the scales.
 struct KqmW4 { i32x4 b[4]; float scv[2], mv[2]; };   // b[2n + hf]: low (n = 0) / high (n = 1) nibbles of q{hf}, the slot order of the A fragments
 struct KqmW6 { i32x4 b[4]; float sc[4]; float d; };  // b[qd], scales[8n + (G&1) + 2 qd] as floats
 
@@ -288,7 +289,51 @@ __device__ __forceinline__ KqmW6 kqm_unpack(const Q6T &w, uint32_t g)
     return u;
 }
 
-// 64 weights of one lane against one column: the arithmetic of q4t_dot / q6t_dot on the unpacked operand
+// Q5_K: the nibbles of q4t with the fifth bit merged in as q5t_dot does (q = nibble | bit << 4, a non-negative byte operand), once
+// per step; scales and mins are Q4_K's, so the columns run kqm_dot(KqmW4) unchanged.
+__device__ __forceinline__ KqmW4 kqm_unpack(const Q5T &w, uint32_t g)
+{
+    constexpr uint32_t M = 0x0F0F0F0Fu, B = 0x10101010u;
+    KqmW4 u;
+#pragma unroll
+    for (int hf = 0; hf < 2; hf++) {
+        const u32x4 q = hf ? w.q1 : w.q0;
+        const uint32_t h = w.qh[hf];
+        u32x4 blo, bhi;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            blo[i] = and_or(h << (4 - i), B, q[i] & M);
+            bhi[i] = and_or(h >> i, B, (q[i] >> 4) & M);
+        }
+        u.b[hf] = __builtin_bit_cast(i32x4, blo);
+        u.b[2 + hf] = __builtin_bit_cast(i32x4, bhi);
+    }
+    const float d = h2f_lo(w.hdr[0]), dmin = h2f_hi(w.hdr[0]);
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        uint32_t sc, mn;
+        k4_scale_min(w.hdr, 2 * g + h, sc, mn);
+        u.scv[h] = d * (float)sc;
+        u.mv[h] = dmin * (float)mn;
+    }
+    return u;
+}
+
+// Q8_0: the quants are the B operands as loaded (signed bytes); d of the lane's four 32-blocks 2h + (G >> 1) widened once.
+struct KqmW8 { i32x4 b[4]; float d[4]; };
+
+__device__ __forceinline__ KqmW8 kqm_unpack(const Q8T &w, uint32_t)
+{
+    KqmW8 u;
+#pragma unroll
+    for (int h = 0; h < 4; h++) {
+        u.b[h] = __builtin_bit_cast(i32x4, w.q[h]);
+        u.d[h] = (h & 1) ? h2f_hi(w.d[h >> 1]) : h2f_lo(w.d[h >> 1]);
+    }
+    return u;
+}
+
+// 64 weights of one lane against one column: the arithmetic of q4t_dot / q6t_dot / q8t_dot on the unpacked operand
 __device__ __forceinline__ float kqm_dot(const KqmW4 &u, const i32x4 (&af)[4], f32x4 sums)
 {
     i32x4 dlo = {0, 0, 0, 0}, dhi = {0, 0, 0, 0};
@@ -316,6 +361,19 @@ __device__ __forceinline__ float kqm_dot(const KqmW6 &u, const i32x4 (&af)[4], f
         tot = fmaf(u.sc[qd], fmaf(-32.0f, sums[qd], v), tot);
     }
     return u.d * tot;
+}
+
+// (Q8_0 has no offset and no min: the sums of x' go unused)
+__device__ __forceinline__ float kqm_dot(const KqmW8 &u, const i32x4 (&af)[4], f32x4)
+{
+    float a = 0.f;
+#pragma unroll
+    for (int h = 0; h < 4; h++) {
+        const i32x4 dq = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[h], u.b[h], i32x4{0, 0, 0, 0}, 0, 0, 0);
+        const float v = fmaf((float)dq[2], 65536.0f, fmaf((float)dq[1], 256.0f, (float)dq[0]));
+        a = fmaf(u.d[h], v, a);
+    }
+    return a;
 }
 
 // Fixed-point staging of ONE 256-element super-block of the activation vector by one wave (lane holds elements 4*lane .. +3, after the

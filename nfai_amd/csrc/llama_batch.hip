@@ -37,7 +37,7 @@ struct Batch {
     Model *mem[BATCH_MAX] = {};
     uint64_t serial[BATCH_MAX] = {};
     uint32_t gen[BATCH_MAX] = {};
-    bool quant = false;            // the members' matrices are Q4_K / Q6_K in the T16 layout (nfai_hip_llama_batch_create_ex, NFAI_BATCH_QUANT)
+    bool quant = false;            // the members' matrices are quantised, in the T16 layout (nfai_hip_llama_batch_create_ex, NFAI_BATCH_QUANT[_ANY])
     StepWords *d_w = nullptr, *h_w = nullptr;   // the step's words on the device | their pinned mirror
     void *d_am = nullptr, *d_attn = nullptr;
     Graph g_io[BATCH_MAX + 1];     // by column count (a batch: its n), captured on first use: [tokens H2D] -> the token -> [results D2H]
@@ -218,10 +218,10 @@ BatchKqArgs batch_kq(const BatchGemvArgs &a, int type)
     return k;
 }
 
-// q|k|v of block l: one launch for fp16 members; for quantised ones by weight type: one launch when the three matrices agree, two when
-// they differ (Q4_K_M files keep attn_v in Q6_K on half of the blocks), so that a launch stages the activations in ONE fragment
-// layout.  Returns the number of launches.
-int batch_qkv(const BatchOps &ops, size_t l, BatchKqArgs (&out)[2])
+// q|k|v of block l: one launch for fp16 members; for quantised ones by weight type, in the fixed order Q4_K, Q5_K, Q6_K, Q8_0: one
+// launch when the three matrices agree, one per type when they differ (Q4_K_M and Q5_K_M files keep attn_v in Q6_K on half of the
+// blocks), so that a launch stages the activations in ONE fragment layout.  Returns the number of launches, three at the most.
+int batch_qkv(const BatchOps &ops, size_t l, BatchKqArgs (&out)[3])
 {
     const BatchGemvArgs base = ops.qkv(l);
     if (!ops.bt->quant) {
@@ -231,7 +231,7 @@ int batch_qkv(const BatchOps &ops, size_t l, BatchKqArgs (&out)[2])
     const Layer &L = ops.bt->mem[0]->layers[l];
     const Tensor *t[3] = {&L.wq, &L.wk, &L.wv};
     int n = 0;
-    for (int type : {NFAI_Q4_K_T16, NFAI_Q6_K_T16}) {
+    for (int type : {NFAI_Q4_K_T16, NFAI_Q5_K_T16, NFAI_Q6_K_T16, NFAI_Q8_0_T16}) {
         BatchKqArgs k = batch_kq(base, type);
         int j = 0;
         for (int i = 0; i < 3; i++) { k.W[i] = nullptr; k.seg_rows[i] = 0; }
@@ -252,7 +252,7 @@ int batch_token(const BatchOps &ops, Gemv gemv, Other other)
     S_TRY(other(KC_OTHER, (size_t)0));
     for (size_t l = 0; l < m0->layers.size(); l++) {
         const Layer &L = m0->layers[l];
-        BatchKqArgs qkv[2];
+        BatchKqArgs qkv[3];
         const int nq = batch_qkv(ops, l, qkv);
         for (int j = 0; j < nq; j++) S_TRY(gemv(KC_QKV, qkv[j]));
         S_TRY(other(KC_ATTN, l));
@@ -382,7 +382,8 @@ int profile_columns(Batch *bt, float *ms_by_class, uint32_t *launches_by_class, 
 
 // One model of a batch or window: what a batch admits as a member (i; the window's model is i = 0), in this order: finalized, a whole
 // model, the fused five-launch path, member 0's KV element type, matrix types (fp16 throughout, or with NFAI_BATCH_QUANT Q4_K / Q6_K
-// in the T16 layout throughout, in any per-tensor mix), member 0's tensors.  quant: the model's matrices are quantised.
+// in the T16 layout throughout, with NFAI_BATCH_QUANT_ANY besides it Q5_K / Q8_0 too, in any per-tensor mix), member 0's tensors.
+// quant: the model's matrices are quantised.
 int admit_member(Model *m, Model *m0, uint32_t i, uint32_t flags, bool window, const char *fn, bool &quant)
 {
     const char *obj = window ? "window" : "batch";
@@ -399,7 +400,7 @@ int admit_member(Model *m, Model *m0, uint32_t i, uint32_t flags, bool window, c
     if (m->kv_f16 != m0->kv_f16)
         return fail(NFAI_ERR_UNSUPPORTED, "%s: %s keeps an %s KV cache, member 0 an %s one; one element type per batch", fn, who,
                     m->kv_f16 ? "fp16" : "fp32", m0->kv_f16 ? "fp16" : "fp32");
-    const bool allow_q = (flags & NFAI_BATCH_QUANT) != 0;
+    const bool allow_q = (flags & NFAI_BATCH_QUANT) != 0, allow_any = (flags & NFAI_BATCH_QUANT_ANY) != 0;
     const char *first16 = nullptr, *firstq = nullptr;
     size_t first16_blk = 0, firstq_blk = 0;
     int firstq_type = 0;
@@ -415,9 +416,15 @@ int admit_member(Model *m, Model *m0, uint32_t i, uint32_t flags, bool window, c
         if (t.type == NFAI_Q4_K || t.type == NFAI_Q6_K)
             return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu (ggml type %d, %llu rows) runs the VALU fallback (rows %% 16 != 0); the batched "
                                               "int8-MFMA kernels take 16-row tiles", fn, who, what, blk, ggml_type_of(t.type), (unsigned long long)t.rows);
-        if (t.type != NFAI_Q4_K_T16 && t.type != NFAI_Q6_K_T16)
+        if (allow_any && (t.type == NFAI_Q5_K || t.type == NFAI_Q8_0))
+            return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu has ggml type %d in its native layout (the VALU fallback); the batched "
+                                              "int8-MFMA kernels take the T16 layout", fn, who, what, blk, ggml_type_of(t.type));
+        if (!allow_any && t.type != NFAI_Q4_K_T16 && t.type != NFAI_Q6_K_T16)
             return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu has ggml type %d; a quantised %s takes Q4_K and Q6_K matrices "
-                                              "(Q5_K and Q8_0 weights decode through nfai_hip_llama_decode_step)", fn, who, what, blk, ggml_type_of(t.type), obj);
+                                              "(Q5_K and Q8_0 weights decode through nfai_hip_llama_decode_step, or in a %s made with "
+                                              "NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY)", fn, who, what, blk, ggml_type_of(t.type), obj, obj);
+        if (!is_t16(t.type)) return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu has ggml type %d; a quantised %s takes Q4_K, Q5_K, "
+                                                               "Q6_K and Q8_0 matrices", fn, who, what, blk, ggml_type_of(t.type), obj);
         if (!firstq) { firstq = what; firstq_blk = blk; firstq_type = ggml_type_of(t.type); }
         return NFAI_OK;
     };
@@ -509,7 +516,11 @@ int columns_alloc(Batch *bt, uint32_t win_tokens, const char *fn)
 static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out, const char *fn, uint32_t win_tokens = 0)
 {
     if (!models || !out) return fail(NFAI_ERR_INVALID, "%s: null argument", fn);
-    if (flags & ~(uint32_t)NFAI_BATCH_QUANT) return fail(NFAI_ERR_INVALID, "%s: invalid flags 0x%x (known: NFAI_BATCH_QUANT = 0x%x)", fn, flags, NFAI_BATCH_QUANT);
+    if (flags & ~(uint32_t)(NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY))
+        return fail(NFAI_ERR_INVALID, "%s: invalid flags 0x%x (known: NFAI_BATCH_QUANT = 0x%x, NFAI_BATCH_QUANT_ANY = 0x%x)", fn, flags,
+                    NFAI_BATCH_QUANT, NFAI_BATCH_QUANT_ANY);
+    if ((flags & NFAI_BATCH_QUANT_ANY) && !(flags & NFAI_BATCH_QUANT))
+        return fail(NFAI_ERR_INVALID, "%s: flags 0x%x: NFAI_BATCH_QUANT_ANY widens NFAI_BATCH_QUANT and is only valid together with it", fn, flags);
     if (n < 1 || n > BATCH_MAX) return fail(NFAI_ERR_INVALID, "%s: invalid n = %u (a batch holds 1 to %u models)", fn, n, BATCH_MAX);
     Model *mem[BATCH_MAX] = {};
     for (uint32_t i = 0; i < n; i++) {

@@ -156,6 +156,7 @@ class LlamaModel:
         self.handle = h
         self._keep = []
         self._quantized = bool(getattr(share_from, "_quantized", False))   # any matrix in a block encoding (picks the window's kernel family)
+        self._any_quant = bool(getattr(share_from, "_any_quant", False))   # any matrix in Q5_K / Q8_0 (the window then needs BATCH_QUANT_ANY)
         self._windows = {}
         if share_from is not None:  # another slot of the same pipeline stage: the donor's weights, no copy, no second repack
             self._donor = share_from
@@ -170,11 +171,15 @@ class LlamaModel:
             ptr, ty, rows, cols = t
             if rows > 1 and ty not in (_lib.F32, _lib.F16):
                 self._quantized = True
+                if ty in (_lib.Q5_K, _lib.Q8_0):
+                    self._any_quant = True
             call("nfai_hip_llama_set_tensor_device", self.handle, name.encode(), ty, rows, cols, C.c_void_p(ptr))
             return
         if isinstance(t, QuantTensor):
             self._quantized = True
             a, ty, (rows, cols) = np.ascontiguousarray(t.data), t.ggml_type, t.shape
+            if ty in (_lib.Q5_K, _lib.Q8_0):
+                self._any_quant = True
         else:
             a = np.ascontiguousarray(t)
             ty = _GGML[a.dtype]
@@ -318,7 +323,7 @@ class LlamaModel:
         self.firstInput = False
         win = self._windows.get(k + 1)
         if win is None:
-            win = self._windows[k + 1] = LlamaWindow(self, k + 1, quantized=self._quantized)
+            win = self._windows[k + 1] = LlamaWindow(self, k + 1, quantized=self._quantized, any_quant=self._any_quant)
         if self.promptPrefill:
             self.Ingest(tokenIds[:-1])
         else:
@@ -388,17 +393,20 @@ class LlamaModel:
 class LlamaBatch:
     """n LlamaModel instances over ONE set of weights advancing together: what n concurrent token loops (LlamaModel.cs:116-125) do,
     with every weight row read once per step (nfai_hip_llama_batch_*).  `models`: 1 to 8 whole fp16 models (quantized=True: or
-    1 to 8 whole models whose matrices are all Q4_K / Q6_K) on one buffer manager,
+    1 to 8 whole models whose matrices are all Q4_K / Q6_K; with any_quant=True besides it: Q5_K and Q8_0 matrices too, in any
+    per-tensor mix of the four) on one buffer manager,
     one of them the donor of the others (`share_from`).  Each member keeps its own KV cache and position and stays a normal
     LlamaModel: Step / Ingest / SetPos on a member between batch steps are seen by the next batch step."""
 
-    def __init__(self, models, quantized: bool = False):
+    def __init__(self, models, quantized: bool = False, any_quant: bool = False):
+        if any_quant and not quantized:
+            raise ValueError("LlamaBatch: any_quant=True widens quantized=True and needs it")
         self.models = list(models)
         self.n = len(self.models)
         hs = (_lib.H * max(self.n, 1))(*[m.handle.value if isinstance(m.handle, _lib.H) else int(m.handle) for m in self.models])
         h = _lib.H()
         if quantized:   # also admits members whose matrices are all Q4_K / Q6_K (Q4_K_M files): the int8-MFMA batch
-            call("nfai_hip_llama_batch_create_ex", hs, self.n, _lib.BATCH_QUANT, C.byref(h))
+            call("nfai_hip_llama_batch_create_ex", hs, self.n, _lib.BATCH_QUANT | (_lib.BATCH_QUANT_ANY if any_quant else 0), C.byref(h))
         else:
             call("nfai_hip_llama_batch_create", hs, self.n, C.byref(h))
         self.handle = h
@@ -454,12 +462,15 @@ class LlamaWindow:
     `Verify` is lossless greedy speculative decoding: guessed tokens ride as extra columns and are kept as far as the model's own
     ArgMax agrees.  The model stays a normal LlamaModel between window calls."""
 
-    def __init__(self, model, max_tokens: int, quantized: bool = False):
+    def __init__(self, model, max_tokens: int, quantized: bool = False, any_quant: bool = False):
+        if any_quant and not quantized:
+            raise ValueError("LlamaWindow: any_quant=True widens quantized=True and needs it")
         self.model = model
         self.max_tokens = int(max_tokens)
         self.V = int(model.dims["V"])
         h = _lib.H()
-        call("nfai_hip_llama_window_create", model.handle, self.max_tokens, _lib.BATCH_QUANT if quantized else 0, C.byref(h))
+        flags = (_lib.BATCH_QUANT if quantized else 0) | (_lib.BATCH_QUANT_ANY if any_quant else 0)
+        call("nfai_hip_llama_window_create", model.handle, self.max_tokens, flags, C.byref(h))
         self.handle = h
 
     def Step(self, tokens, want_logits: bool = True):

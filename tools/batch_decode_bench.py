@@ -21,6 +21,12 @@ the oracle, which takes about a minute of host time).  One JSON line; --out writ
 --quant q4_k_m: the same run on llama.cpp's Q4_K_M tensor mix (bench.gen_weights_hbm's random K-quant super-blocks; Q4_K with Q6_K
 for token_embd / output and for attn_v / ffn_down of the blocks llama.cpp keeps there), through the int8-MFMA batch
 (LlamaBatch(..., quantized=True), nfai_hip_llama_batch_create_ex); the oracle walks the dequantised weights.
+
+--quant q5_k_m | q8_0: the same on the Q5_K_M mix of tools/q5_k_bench.py and the Q8_0 weights of tools/q8_0_bench.py (their
+generators), through LlamaBatch(..., quantized=True, any_quant=True) (NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY).
+
+    python tools/batch_decode_bench.py --quant q5_k_m --out profiles/batch_decode_q5_k_m.json
+    python tools/batch_decode_bench.py --quant q8_0 --out profiles/batch_decode_q8_0.json
 """
 import argparse
 import json
@@ -32,7 +38,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 HBM_PEAK = 8.0e12
 T, WARM, NMAX = 512, 5, 8
@@ -58,12 +64,38 @@ def spread(xs):
     return (max(xs) - min(xs)) / statistics.median(xs)
 
 
-def run_model(torch, dims, steps, windows, quant="f16"):
+ANY_QUANT = ("q5_k_m", "q8_0")   # the encodings a batch takes with any_quant=True
+
+
+def gen_weights(torch, dims, quant):
+    """name -> (device tensor, ggml type, rows, cols) in the encoding `quant`."""
+    if quant == "q5_k_m":
+        import q5_k_bench
+        return q5_k_bench.gen_q5_k_m_weights_hbm(torch, dims)
+    if quant == "q8_0":
+        import q8_0_bench
+        return q8_0_bench.gen_q8_0_weights_hbm(torch, dims)
     import bench as B
+    return B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant=quant)
+
+
+def host_weights(weights, quant):
+    """What the oracle takes: every quantised matrix dequantised to fp32."""
+    if quant == "q5_k_m":
+        import q5_k_bench
+        return {k: q5_k_bench.dequant(t, ty, r, c) for k, (t, ty, r, c) in weights.items()}
+    if quant == "q8_0":
+        import q8_0_bench
+        return {k: (q8_0_bench.dequant_q8_0(t.cpu().numpy(), r, c) if ty == q8_0_bench.Q8_0 else t.cpu().numpy()) for k, (t, ty, r, c) in weights.items()}
+    import bench as B
+    return B.host_weights(weights)
+
+
+def run_model(torch, dims, steps, windows, quant="f16"):
     from nfai_amd import synth
     from nfai_amd.hip import HipBufferManager
     from nfai_amd.llama_model import LlamaBatch, LlamaModel
-    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant=quant)
+    weights = gen_weights(torch, dims, quant)
     C = T + WARM + steps + 16
     mgr = HipBufferManager(0)
     dd = dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0)
@@ -90,7 +122,7 @@ def run_model(torch, dims, steps, windows, quant="f16"):
     out = {"model": dims.name, "weights": quant, "kv_cache": "f32", "positions": [p0, p0 + steps - 1], "steps_per_window": steps, "by_n": {}}
     for n in (1, 2, 4, 8):
         ms = members[:n]
-        batch = LlamaBatch(ms, quantized=quant != "f16")
+        batch = LlamaBatch(ms, quantized=quant != "f16", any_quant=quant in ANY_QUANT)
 
         def batch_window():
             rewind(ms)
@@ -173,12 +205,11 @@ def run_model(torch, dims, steps, windows, quant="f16"):
 
 def oracle_parity(torch, dims, n=4, quant="f16"):
     """n = 4 on full-size weights at shallow staggered depths (the oracle walks every earlier token on the host): max |dlogit| over 4 steps."""
-    import bench as B
     import oracle as orc
     from nfai_amd import synth
     from nfai_amd.hip import HipBufferManager
     from nfai_amd.llama_model import LlamaBatch, LlamaModel
-    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant=quant)
+    weights = gen_weights(torch, dims, quant)
     C = 32
     mgr = HipBufferManager(0)
     dd = dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0)
@@ -187,7 +218,7 @@ def oracle_parity(torch, dims, n=4, quant="f16"):
     ms = [LlamaModel(mgr, md, wt, C, dims=dd)]
     for _ in range(1, n):
         ms.append(LlamaModel(mgr, md, wt, C, dims=dd, share_from=ms[0]))
-    host = B.host_weights(weights)   # K-quant matrices dequantised
+    host = host_weights(weights, quant)   # quantised matrices dequantised
     toks = [synth.make_tokens(dims, 24, seed=400 + s) for s in range(n)]
     refs = []
     for s in range(n):
@@ -196,7 +227,7 @@ def oracle_parity(torch, dims, n=4, quant="f16"):
             ms[s].Step(int(t), want_logits=False)
             ref.step(int(t), want_logits=False)
         refs.append(ref)
-    batch = LlamaBatch(ms, quantized=quant != "f16")
+    batch = LlamaBatch(ms, quantized=quant != "f16", any_quant=quant in ANY_QUANT)
     worst, top, same = 0.0, 0.0, []
     for i in range(4):
         st = [int(toks[s][2 + 3 * s + i]) for s in range(n)]
@@ -219,7 +250,7 @@ def main():
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--only", default="", metavar="MODEL", help="one model, e.g. llama-3.2-3b")
-    ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m"], help="weight encoding (q4_k_m: the int8-MFMA batch)")
+    ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m", "q5_k_m", "q8_0"], help="weight encoding (all but f16: the int8-MFMA batch)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch

@@ -21,6 +21,8 @@ What is NOT measured: how often an n-gram drafter is right on real text.  The we
     python tools/spec_decode_bench.py --out profiles/spec_decode.json
     python tools/spec_decode_bench.py --quant q4_k_m --out profiles/spec_decode_q4_k_m.json
     python tools/spec_decode_bench.py --depth 8192 --only llama-3.2-3b --out profiles/spec_decode_deep.json
+
+--quant q5_k_m | q8_0: the weights of tools/q5_k_bench.py / tools/q8_0_bench.py, window and batch made with any_quant=True.
 """
 import argparse
 import json
@@ -32,7 +34,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 WARM, NMAX, E2E_TOKENS = 5, 8, 256
 CLASSES = ["qkv", "attn", "wo", "gateup", "down", "lmhead", "other"]
@@ -47,11 +49,12 @@ def per_launch(prof):
 
 
 def run_model(torch, dims, depth, steps, windows, quant):
-    import bench as B
+    from batch_decode_bench import ANY_QUANT, gen_weights
     from nfai_amd import synth
     from nfai_amd.hip import HipBufferManager
     from nfai_amd.llama_model import LlamaBatch, LlamaModel, LlamaWindow
-    weights = B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant=quant)
+    weights = gen_weights(torch, dims, quant)
+    any_quant = quant in ANY_QUANT
     C = depth + WARM + E2E_TOKENS + 32
     mgr = HipBufferManager(0)
     dd = dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0)
@@ -71,7 +74,7 @@ def run_model(torch, dims, depth, steps, windows, quant):
         first.append(tok)
     p0 = depth + WARM
     m0 = members[0]
-    win = LlamaWindow(m0, NMAX, quantized=quant != "f16")
+    win = LlamaWindow(m0, NMAX, quantized=quant != "f16", any_quant=any_quant)
     out = {"model": dims.name, "weights": quant, "kv_cache": "f32", "first_position": p0, "steps_per_window": steps, "by_T": {}}
 
     # the batch-1 path over the positions of the end-to-end runs, and the plain greedy continuation through the window (k = 0)
@@ -92,7 +95,7 @@ def run_model(torch, dims, depth, steps, windows, quant):
 
     for T in (2, 4, 8):
         ms = members[:T]
-        batch = LlamaBatch(ms, quantized=quant != "f16")
+        batch = LlamaBatch(ms, quantized=quant != "f16", any_quant=any_quant)
         cols = [int(t) for t in synth.make_tokens(dims, T, seed=7 + T)]
 
         def batch_window():
@@ -180,7 +183,7 @@ def main():
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--depth", type=int, default=512, help="tokens ingested before the measurement (8192: the deep-context run)")
     ap.add_argument("--only", default="", metavar="MODEL", help="one model, e.g. llama-3.2-3b")
-    ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m"])
+    ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m", "q5_k_m", "q8_0"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
