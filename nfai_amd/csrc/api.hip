@@ -239,6 +239,15 @@ NFAI_API int32_t nfai_hip_debug_xcd_shares(nfai_ctx_t h, const uint16_t *shares8
 // GEMV launches that took the XD instantiations (rows dealt by share) since the library was loaded, on any context.
 NFAI_API uint64_t nfai_hip_debug_gemv_dealt(void) { return gemv_dealt_launches(); }
 
+// Which prefill GEMM configurations ran: one descriptor of 16 words per k_gemm_f16 / k_gemm_f16_glds launch since the last call, on
+// any context, oldest first — BM, BN, WM, WN, BK, stages, weight-ring stages, KS, pipelined, LDS-staged (0 = register-staged),
+// epilogue, batch, ksplit, M, N, K (GemmDesc).  Returns the number written (at most max_desc, the newest ones).
+NFAI_API uint32_t nfai_hip_debug_gemm_last(uint32_t *desc16, uint32_t max_desc)
+{
+    static_assert(sizeof(GemmDesc) == 16 * sizeof(uint32_t), "sixteen words per launch");
+    return desc16 ? gemm_last(reinterpret_cast<GemmDesc *>(desc16), max_desc) : 0;
+}
+
 static int canary_check_all(Ctx *c);  // NFAI_HIP_DEBUG_CANARY (below, with nfai_hip_buf_alloc)
 
 NFAI_API int32_t nfai_hip_ctx_synchronize(nfai_ctx_t h)

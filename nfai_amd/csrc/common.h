@@ -212,6 +212,14 @@ struct GemmArgs {  // C[M][N] (+R) = alpha * A[M][K] * B[N][K]^T, fp16 operands,
     uint32_t causal = 0, causal_pos0 = 0;  // 1: C is a causal score matrix, 2: A is a causal probability matrix (skip masked tiles)
 };
 hipError_t launch_gemm_f16(const GemmArgs &a, hipStream_t s);
+// Test hook (nfai_hip_debug_gemm_last): what one k_gemm_f16 / k_gemm_f16_glds launch was instantiated with, sixteen words.
+struct GemmDesc {
+    uint32_t BM, BN, WM, WN, BK;
+    uint32_t stages, stages_b;   // LDS stages of the A / B ring (direct-to-LDS) or register sets (register-staged: both = RING)
+    uint32_t KS, pipe, lds_staged, epi, batch, ksplit, M, N, K;
+};
+constexpr uint32_t GEMM_RING_N = 256;
+uint32_t gemm_last(GemmDesc *out, uint32_t max_desc);  // the launches since the last call, oldest first (the newest GEMM_RING_N at most)
 hipError_t launch_gemm_kq(const GemmArgs &a, hipStream_t s);   // dequant-in-LDS GEMM on T16 K-quant weights
 hipError_t launch_f32_to_f16(const float *x, void *y_f16, uint64_t n, hipStream_t s);
 hipError_t launch_sum_slabs(const float *slabs, uint32_t ks, uint64_t n, const float *R, float *C, hipStream_t s);  // C = R + sum of ks slabs of n floats

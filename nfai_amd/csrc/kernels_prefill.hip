@@ -21,6 +21,8 @@
 //   (22.5 % of the dense fp16 peak over a whole 512-token prefill at 3B, gate|up 890 TFLOP/s).
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "common.h"
 
 namespace nfai {
@@ -867,6 +869,28 @@ __global__ __launch_bounds__(WM *WN *KS * 64) void k_gemm_f16_glds(const GemmPar
 #undef GEMM_TICK
 }
 
+// Test hook (nfai_hip_debug_gemm_last): the configuration of every gemm_launch / gemm_launch_glds call, in a ring of host words —
+// tests prove through it which branch of gemm_pick / gemm_pick_rope their shape reached.  Sixteen words per launch (GemmDesc).
+static GemmDesc g_gemm_ring[GEMM_RING_N];
+static std::atomic<uint32_t> g_gemm_head{0}, g_gemm_tail{0};  // launches noted / launches already read
+
+static void gemm_note(uint32_t BM, uint32_t BN, uint32_t WM, uint32_t WN, uint32_t BK, uint32_t stages, uint32_t stages_b, uint32_t KS,
+                      bool pipe, bool lds_staged, uint32_t epi, uint32_t batch, const GemmParams &p)
+{
+    const uint32_t i = g_gemm_head.fetch_add(1, std::memory_order_relaxed);
+    g_gemm_ring[i % GEMM_RING_N] = GemmDesc{BM, BN, WM, WN, BK, stages, stages_b, KS, pipe, lds_staged, epi, batch, p.ksplit, p.M, p.N, p.K};
+}
+
+uint32_t gemm_last(GemmDesc *out, uint32_t max_desc)
+{
+    const uint32_t head = g_gemm_head.load(std::memory_order_relaxed);
+    uint32_t tail = g_gemm_tail.exchange(head, std::memory_order_relaxed);
+    if (head - tail > GEMM_RING_N) tail = head - GEMM_RING_N;   // the ring holds the newest GEMM_RING_N
+    if (head - tail > max_desc) tail = head - max_desc;
+    for (uint32_t i = tail; i != head; i++) out[i - tail] = g_gemm_ring[i % GEMM_RING_N];
+    return head - tail;
+}
+
 template <int BM, int BN, int WM, int WN, int EPI, int NST, int BK = 64, bool PIPE = false, int NSTB = NST, int KS = 1>
 static hipError_t gemm_launch_glds(const GemmParams &p, uint32_t batch, hipStream_t s)
 {
@@ -874,6 +898,7 @@ static hipError_t gemm_launch_glds(const GemmParams &p, uint32_t batch, hipStrea
     constexpr int LDS = (NST * BM + NSTB * BN) * BK * 2;
     static_assert(LDS <= 160 * 1024, "LDS of one CU");
     if (p.K % BK) return hipErrorInvalidValue;
+    gemm_note(BM, BN, WM, WN, BK, NST, NSTB, KS, PIPE, true, EPI, batch, p);
     auto kern = k_gemm_f16_glds<BM, BN, WM, WN, EPI, NST, BK, PIPE, NSTB, KS>;
     static bool attr_set = false;
     if (LDS > 64 * 1024 && !attr_set) {
@@ -896,6 +921,7 @@ template <int BM, int BN, int WM, int WN, int BK, int EPI, int KS = 1, int RING 
 static hipError_t gemm_launch(const GemmParams &p, uint32_t batch, hipStream_t s)
 {
     constexpr int LDS = 2 * (BM + BN) * BK * 2;
+    gemm_note(BM, BN, WM, WN, BK, RING, RING, KS, false, false, EPI, batch, p);
     auto kern = k_gemm_f16<BM, BN, WM, WN, BK, EPI, KS, RING>;
     if (LDS > 64 * 1024) {
         static bool attr_set = false;

@@ -59,8 +59,12 @@ LLAMA_31_8B = LlamaDims("llama-3.1-8b", 4096, 32, 32, 8, 128, 14336, 128256, Fal
 # Small shapes for CPU-sized parity runs (all K multiples of 256 so K-quants apply).
 TINY = LlamaDims("tiny-llama", 256, 2, 4, 2, 64, 512, 512, True)
 TINY_D128 = LlamaDims("tiny-llama-d128", 512, 3, 4, 2, 128, 1024, 768, False)
+# Thin two-block models whose prefill GEMMs take the tile configurations of the published widths (tests/test_gpu_prefill_rows.py):
+# F = 8192 gives gate|up and Wdown the wide forms and the K splits; (H + 2 Hkv) D = 1920 is a multiple of 80 and of 48.
+THIN_F8192 = LlamaDims("thin-f8192", 256, 2, 4, 2, 64, 8192, 512, True)
+THIN_H9 = LlamaDims("thin-h9-d128", 256, 2, 9, 3, 128, 512, 512, True)
 
-BY_NAME = {d.name: d for d in (LLAMA_32_1B, LLAMA_32_3B, LLAMA_31_8B, TINY, TINY_D128)}
+BY_NAME ={d.name: d for d in (LLAMA_32_1B, LLAMA_32_3B, LLAMA_31_8B, TINY, TINY_D128)}
 
 
 def make_weights(dims: LlamaDims, seed: int = 1234, std: float = 0.02) -> dict:
