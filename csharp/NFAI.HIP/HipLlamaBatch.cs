@@ -40,6 +40,34 @@ public sealed unsafe class HipLlamaBatch : IDisposable
             Native.Check(Native.nfai_hip_llama_batch_step(handle, t, logits.IsEmpty ? null : l, a));
     }
 
+    /// <summary>One token per member as Step (LlamaModel.cs:116-125), then every member's candidates of the reference's default sampler
+    /// formed on the device (SamplingUtils.cs:5-13: values / temperature, softmax over Vocab, stable descending order, Take(k)):
+    /// ids[i * k ..] and probs[i * k ..] are member i's k most probable tokens, what nfai_hip_llama_decode_topk returns for one model.
+    /// One graph launch and one synchronisation; 520 bytes per member cross PCIe instead of Vocab floats.</summary>
+    public void StepTopK(ReadOnlySpan<uint> tokens, float temperature, uint k, Span<uint> ids, Span<float> probs)
+    {
+        if (tokens.Length != Count) throw new ArgumentException("one token per member", nameof(tokens));
+        if (ids.Length != Count * k || probs.Length != Count * k) throw new ArgumentException("ids and probs are [Count][k]");
+        fixed (uint* t = tokens) fixed (uint* i = ids) fixed (float* p = probs)
+            Native.Check(Native.nfai_hip_llama_batch_step_topk(handle, t, temperature, k, i, p));
+    }
+
+    private const uint TopK = 40;                                   // SamplingUtils.cs:5 defaults
+    private const float Temperature = 0.5f, TopPValue = 0.95f;
+
+    /// <summary>One token per member with the reference's default sampler (LlamaModel.cs:128-130,165): StepTopK, then per member, in
+    /// member order, the nucleus cut and the draw of SamplingUtils.cs:14-31 with Random.Shared.NextSingle().  next[i] is member i's
+    /// sampled token.</summary>
+    public void StepSampled(ReadOnlySpan<uint> tokens, Span<uint> next)
+    {
+        if (next.Length != Count) throw new ArgumentException("one slot per member", nameof(next));
+        var ids = new uint[Count * TopK]; var probs = new float[Count * TopK];
+        StepTopK(tokens, Temperature, TopK, ids, probs);
+        for (int i = 0; i < Count; i++)
+            next[i] = HipLlamaModel.TopPFromCandidates(ids.AsSpan(i * (int)TopK, (int)TopK).ToArray(), probs.AsSpan(i * (int)TopK, (int)TopK).ToArray(),
+                                                       TopPValue, Random.Shared.NextSingle());
+    }
+
     /// <summary>nSteps tokens per member with every member's ArgMax fed back on the device (SamplingUtils.cs:43-57 in place of TopP):
     /// tokensOut[s * Count + i] is member i's token after step s.</summary>
     public void Greedy(ReadOnlySpan<uint> firstTokens, uint nSteps, Span<uint> tokensOut)

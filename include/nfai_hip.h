@@ -158,6 +158,13 @@ int32_t nfai_hip_argmax(nfai_ctx_t ctx, nfai_buf_t x, uint32_t n, nfai_buf_t out
  * probs_out[k] (host arrays; k <= 64, the reference's topK is 40).  One launch over the logits and 8k + 8 bytes back instead of n
  * floats; the nucleus cut and the Random.Shared draw (:14-31) stay with the caller.  Blocking. */
 int32_t nfai_hip_topk(nfai_ctx_t ctx, nfai_buf_t x, uint32_t n, float temperature, uint32_t k, uint32_t *ids_out, float *probs_out);
+/* nfai_hip_topk for `rows` (1..8) vectors of n floats: SamplingUtils.TopP's candidate half (SamplingUtils.cs:7-13) once per row, in ONE
+ * pair of launches and one copy back.  x[r] is row r's buffer (rows need not be adjacent in memory; the same buffer may be named more
+ * than once); row r's candidates land in ids_out[r * k ..], probs_out[r * k ..] and are bit-identical to nfai_hip_topk on x[r].
+ * NFAI_ERR_INVALID: what nfai_hip_topk refuses (k outside [1, min(64, n)], temperature not > 0, n = 0), rows outside [1, 8], a dead
+ * buffer, a buffer shorter than n floats, rows * n beyond the context's top-k scratch.  Blocking. */
+int32_t nfai_hip_topk_rows(nfai_ctx_t ctx, const nfai_buf_t *x /* [rows] */, uint32_t rows, uint32_t n, float temperature, uint32_t k,
+                           uint32_t *ids_out /* [rows][k] */, float *probs_out /* [rows][k] */);
 
 /* ---- fused operators (no reference counterpart: each replaces the chain named) ---- */
 /* scores -> softmax -> weighted sum in one KV-cache pass, GQA heads sharing each K/V read.
@@ -373,7 +380,7 @@ int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_t n, nfai
  * to it.  NFAI_ERR_UNSUPPORTED under the flag(s), naming member, tensor and ggml type: Q5_K / Q8_0 matrices without
  * NFAI_BATCH_QUANT_ANY, fp16 and quantised matrices in one model, a quantised matrix whose row count is not a multiple of 16 (the
  * VALU fallback), a shape the kernels' LDS plan does not hold, and every refusal of _batch_create.
- * The handle works with _batch_step, _batch_greedy, _batch_bytes_per_token (quantised bytes: every T16 plane and norm gain once, an
+ * The handle works with _batch_step, _batch_step_topk, _batch_greedy, _batch_bytes_per_token (quantised bytes: every T16 plane and norm gain once, an
  * embedding row per member where the table is not the head's, each member's KV rows), _batch_profile_step and _batch_destroy. */
 enum nfai_batch_flags {
     NFAI_BATCH_QUANT     = 1u << 0,   /* admit members whose matrices are all Q4_K / Q6_K */
@@ -390,6 +397,19 @@ int32_t nfai_hip_llama_batch_destroy(nfai_batch_t batch);
  * enqueued, no member's position moves.  A member destroyed or re-finalized since _batch_create: NFAI_ERR_INVALID. */
 int32_t nfai_hip_llama_batch_step(nfai_batch_t batch, const uint32_t *tokens /* [n] */, float *logits_host /* [n][V] or NULL */,
                                   uint32_t *argmax /* [n] */);
+/* ≙ one pass of the loop body LlamaModel.cs:116-125 for every member, as _batch_step, then for every member the candidates of the
+ * reference's DEFAULT sampler (LlamaModel.cs:128-130,165 call SamplingUtils.TopP on the V logits read back to the host): member i's
+ * k most probable tokens under softmax(logits / temperature) and their probabilities (SamplingUtils.cs:5-13) in ids_out[i * k ..],
+ * probs_out[i * k ..], exactly what nfai_hip_llama_decode_topk returns for one model and nfai_hip_topk for member i's logits.  The
+ * caller finishes TopP per member (SamplingUtils.cs:14-31: nucleus, renormalise, draw).  Blocking: token words in from pinned memory,
+ * ONE hipGraphLaunch (the token's launches, two candidate launches for all members, the result words and 520 bytes per member back),
+ * one synchronisation; the graph is re-captured when (temperature, k) change.  fp16 and quantised batches alike.  Every argument is
+ * checked before anything is enqueued, and a refused call moves no member's position: NFAI_ERR_INVALID for a NULL pointer, a
+ * token >= n_vocab, k outside [1, min(64, n_vocab)], a temperature that is not > 0 (NaN included), a member destroyed or re-finalized
+ * since _batch_create; NFAI_ERR_KV_FULL for a member at its KV capacity.  Afterwards every member is where _batch_step leaves it:
+ * position + 1, logits readable with nfai_hip_llama_read, usable by _decode_step / _batch_step / _batch_greedy. */
+int32_t nfai_hip_llama_batch_step_topk(nfai_batch_t batch, const uint32_t *tokens /* [n] */, float temperature, uint32_t k,
+                                       uint32_t *ids_out /* [n][k] */, float *probs_out /* [n][k] */);
 /* ≙ n_steps passes of LlamaModel.cs:116-125 per member with ArgMax in place of TopP (SamplingUtils.cs:43-57) and the token fed back on
  * the device, as nfai_hip_llama_decode_greedy: member i's ArgMax of step s is its token of step s + 1.  tokens_out[s * n + i]. */
 int32_t nfai_hip_llama_batch_greedy(nfai_batch_t batch, const uint32_t *first_tokens /* [n] */, uint32_t n_steps,

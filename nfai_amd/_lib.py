@@ -84,6 +84,7 @@ SIGNATURES = {
     "nfai_hip_add": [H, H, H, H, u32],
     "nfai_hip_argmax": [H, H, u32, H],
     "nfai_hip_topk": [H, H, u32, f32, u32, C.POINTER(u32), C.POINTER(f32)],
+    "nfai_hip_topk_rows": [H, C.POINTER(H), u32, u32, f32, u32, C.POINTER(u32), C.POINTER(f32)],
     "nfai_hip_attn_decode": [H, H, H, H, H, u32, u32, u32, u32, u32, i32],
     "nfai_hip_gemv_fused": [H, H, i32, H, H, f32, H, H, u32, u32],
     "nfai_hip_lmhead_argmax": [H, H, i32, H, H, f32, H, H, u32, u32],
@@ -120,6 +121,7 @@ SIGNATURES = {
     "nfai_hip_llama_batch_create_ex": [C.POINTER(H), u32, u32, C.POINTER(H)],
     "nfai_hip_llama_batch_destroy": [H],
     "nfai_hip_llama_batch_step": [H, C.POINTER(u32), C.POINTER(f32), C.POINTER(u32)],
+    "nfai_hip_llama_batch_step_topk": [H, C.POINTER(u32), f32, u32, C.POINTER(u32), C.POINTER(f32)],
     "nfai_hip_llama_batch_greedy": [H, C.POINTER(u32), u32, C.POINTER(u32)],
     "nfai_hip_llama_batch_bytes_per_token": [H, C.POINTER(u64)],
     "nfai_hip_llama_batch_profile_step": [H, C.POINTER(u32), C.POINTER(f32), C.POINTER(u32)],

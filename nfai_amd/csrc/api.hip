@@ -134,13 +134,18 @@ NFAI_API int32_t nfai_hip_abi_version(void) { return NFAI_HIP_ABI_VERSION; }
 //   [0, 4 KB)           k_argmax partials + ticket                 (nfai_hip_argmax)
 //   [4 KB, 16 KB)       fused lm_head + ArgMax partials + ticket   (nfai_hip_lmhead_argmax)
 //   [16 KB, 1 MB)       attention tickets + slice partials         (nfai_hip_attn_decode, _gemv_qkv_rope, _engine_block)
-//   [1 MB, 4 MB - 4 KB) top-k workspace                            (nfai_hip_topk)
+//   [1 MB, 4 MB - 4 KB) top-k workspace                            (nfai_hip_topk; nfai_hip_topk_rows: a slice per row from the same
+//                       start, and at the END of the range, from SCR_TOPK_OUT, the rows' contiguous output array.  Slice 0 IS the
+//                       single-vector workspace: its counters are re-armed by whichever launch used them last.  Where slices 1..7
+//                       lie depends on n, and another n's slices or a single-vector call's lists may cover them: _topk_rows zeroes
+//                       the counters of the slices it uses in front of every launch, so no user of the range owes it anything)
 //   [4 MB - 4 KB, 4 MB) cos/sin table of the position | position word (last 256 bytes)
 constexpr size_t SCRATCH_BYTES = 4u << 20;
 constexpr size_t SCR_ARGMAX = 0, SCR_ARGMAX_END = 4096;
 constexpr size_t SCR_LMHEAD = 4096, SCR_LMHEAD_END = 16384;
 constexpr size_t SCR_ATTN = 16384, SCR_ATTN_END = 1u << 20;
 constexpr size_t SCR_TOPK = 1u << 20, SCR_TOPK_END = SCRATCH_BYTES - 4096;
+constexpr size_t SCR_TOPK_OUT = SCR_TOPK_END - ((BATCH_MAX * sizeof(TopkOut) + 255) & ~(size_t)255);   // [BATCH_MAX] TopkOut
 constexpr size_t SCR_ROPECS = SCRATCH_BYTES - 4096, SCR_POS = SCRATCH_BYTES - 256;
 static_assert(2 * ARGMAX_BLOCKS * 4 + 256 <= SCR_ARGMAX_END - SCR_ARGMAX, "k_argmax partials");
 static_assert(argmax_fused_bytes() <= SCR_LMHEAD_END - SCR_LMHEAD, "fused lm_head + ArgMax workspace");
@@ -742,7 +747,7 @@ int topk_run(Ctx *c, const float *logits_dev, uint32_t n, float temperature, uin
     if (!(temperature > 0.f)) return fail(NFAI_ERR_INVALID, "topk: temperature %g (the reference divides by it, SamplingUtils.cs:7)", temperature);
     hipError_t e = launch_topk(logits_dev, n, temperature, k, work, c->stream);
     if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? NFAI_ERR_INVALID : NFAI_ERR_HIP, "topk launch failed: %s", hipGetErrorString(e));
-    struct { float v[TOPK_MAX]; uint32_t i[TOPK_MAX]; float M, S; } out;  // the head of the workspace behind its ticket words (320 + 8 bytes used at k = 40)
+    TopkOut out;  // the head of the workspace behind its ticket words (320 + 8 bytes used at k = 40)
     HIP_TRY(hipMemcpyAsync(&out, static_cast<const char *>(work) + topk_out_offset(), sizeof(out), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     topk_finish(out.v, out.i, out.M, out.S, temperature, k, ids_out, probs_out);
@@ -756,8 +761,47 @@ NFAI_API int32_t nfai_hip_topk(nfai_ctx_t h, nfai_buf_t x, uint32_t n, float tem
     BUF_OR_FAIL(bx, x);
     if (n == 0) return fail(NFAI_ERR_INVALID, "topk: n=0");
     NEED(bx, n, 4);
-    if (topk_work_bytes(n) > SCR_TOPK_END - SCR_TOPK) return fail(NFAI_ERR_INVALID, "topk: n=%u too large for the context scratch", n);
+    // (the range ends at SCR_TOPK_OUT since the rows form keeps its output array behind it: 4352 bytes less than before, and no n
+    // is answered differently, because topk_work_bytes never exceeds 312 KB of the 3 MB)
+    if (topk_work_bytes(n) > SCR_TOPK_OUT - SCR_TOPK) return fail(NFAI_ERR_INVALID, "topk: n=%u too large for the context scratch", n);
     return topk_run(c, static_cast<const float *>(bx->ptr), n, temperature, k, static_cast<char *>(c->scratch) + SCR_TOPK, ids_out, probs_out);
+}
+
+// nfai_hip_topk for 1..BATCH_MAX vectors in one pair of launches and one copy back (launch_topk_rows); per row SamplingUtils.cs:7-13.
+NFAI_API int32_t nfai_hip_topk_rows(nfai_ctx_t h, const nfai_buf_t *x, uint32_t rows, uint32_t n, float temperature, uint32_t k,
+                                    uint32_t *ids_out, float *probs_out)
+{
+    CTX_OR_FAIL(c, h);
+    if (!x || !ids_out || !probs_out) return fail(NFAI_ERR_INVALID, "topk_rows: null argument");
+    if (rows < 1 || rows > BATCH_MAX) return fail(NFAI_ERR_INVALID, "topk_rows: rows=%u outside [1, %u]", rows, BATCH_MAX);
+    if (n == 0) return fail(NFAI_ERR_INVALID, "topk_rows: n=0");
+    if (k == 0 || k > TOPK_MAX || k > n) return fail(NFAI_ERR_INVALID, "topk_rows: k=%u outside [1, min(%u, n=%u)]", k, TOPK_MAX, n);
+    if (!(temperature > 0.f)) return fail(NFAI_ERR_INVALID, "topk_rows: temperature %g (the reference divides by it, SamplingUtils.cs:7)", temperature);
+    TopkRowsArgs a;
+    for (uint32_t r = 0; r < rows; r++) {   // (the same buffer may stand for several rows)
+        Buf *bx = buf_of(x[r]);
+        if (!bx) return fail(NFAI_ERR_INVALID, "topk_rows: invalid buffer handle (row %u)", r);
+        if ((uint64_t)n * 4 > bx->bytes)
+            return fail(NFAI_ERR_INVALID, "topk_rows: the buffer of row %u holds %llu bytes, needs %llu", r, (unsigned long long)bx->bytes, (unsigned long long)n * 4);
+        a.x[r] = static_cast<const float *>(bx->ptr);
+    }
+    const size_t stride = topk_rows_stride(n);
+    if ((uint64_t)rows * stride > SCR_TOPK_OUT - SCR_TOPK)
+        return fail(NFAI_ERR_INVALID, "topk_rows: %u rows of n=%u (%zu bytes each) do not fit the context scratch", rows, n, stride);
+    char *work = static_cast<char *>(c->scratch) + SCR_TOPK;
+    // A slice's ticket and candidate counter must read zero in front of a launch.  Each row's last workgroup leaves them so, but the
+    // slices of another n (or a single-vector call's lists) may have covered the place this n puts them: zero the words of slices
+    // 1 .. rows - 1 (slice 0 is the single-vector workspace, always re-armed).  16 bytes each; this entry point is not a hot path.
+    for (uint32_t r = 1; r < rows; r++) HIP_TRY(hipMemsetAsync(work + r * stride, 0, 16, c->stream));
+    TopkOut *out_dev = reinterpret_cast<TopkOut *>(static_cast<char *>(c->scratch) + SCR_TOPK_OUT);
+    const hipError_t e = launch_topk_rows(a, rows, n, temperature, k, work, out_dev, c->stream);
+    if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? NFAI_ERR_INVALID : NFAI_ERR_HIP, "topk_rows launch failed: %s", hipGetErrorString(e));
+    TopkOut out[BATCH_MAX];
+    HIP_TRY(hipMemcpyAsync(out, out_dev, rows * sizeof(TopkOut), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t r = 0; r < rows; r++)
+        topk_finish(out[r].v, out[r].i, out[r].M, out[r].S, temperature, k, ids_out + (size_t)r * k, probs_out + (size_t)r * k);
+    return NFAI_OK;
 }
 
 // ---- fused operators -------------------------------------------------------------------------

@@ -422,6 +422,16 @@ inline uint32_t topk_blocks(uint32_t n)
 size_t topk_work_bytes(uint32_t n);
 size_t topk_out_offset();
 hipError_t launch_topk(const float *x, uint32_t n, float temperature, uint32_t k, void *work, hipStream_t s);
+// The same for R <= BATCH_MAX vectors of n floats in ONE pair of launches, grid (topk_blocks(n), R): row r reads x[r] (the rows need
+// not be contiguous, and may repeat), keeps ticket, candidate counter, heads, sums and candidates in its own slice of `work` (at
+// r * topk_rows_stride(n); R slices, zeroed once) and leaves its TopkOut in out[r] of one contiguous device array.  Per row the
+// arithmetic, the range partition and the order of the sums are launch_topk's: a row's result is bit-identical to it.
+struct TopkOut { float v[TOPK_MAX]; uint32_t i[TOPK_MAX]; float M, S; };   // what one vector leaves for the host half (topk_finish)
+struct TopkRowsArgs {
+    const float *x[BATCH_MAX] = {};
+};
+inline size_t topk_rows_stride(uint32_t n) { return (topk_work_bytes(n) + 255) & ~(size_t)255; }
+hipError_t launch_topk_rows(const TopkRowsArgs &rows, uint32_t R, uint32_t n, float temperature, uint32_t k, void *work, TopkOut *out, hipStream_t s);
 // launch + 8k + 8 bytes back + the host half (api.hip); blocking
 void topk_finish(const float *vals, const uint32_t *ids, float M, float S, float temperature, uint32_t k, uint32_t *ids_out, float *probs_out);
 int topk_run(Ctx *c, const float *logits_dev, uint32_t n, float temperature, uint32_t k, void *work, uint32_t *ids_out, float *probs_out);

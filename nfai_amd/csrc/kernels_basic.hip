@@ -300,24 +300,26 @@ hipError_t launch_argmax(const float *x, uint32_t n, uint32_t *out_idx, void *pa
 // Round 3's single launch extracted k elements per wave by k rounds of wave-wide maximum and merged the lists by k more rounds
 // in one workgroup: 1.5 us per k (66 us at k = 40, rocprofv3); this form has no loop over k.  NaN-free, finite logits assumed
 // (as k_argmax).  Fewer than k ranges (n < 4096): tau = -inf, every logit is a candidate.
+// launch_topk_rows runs the same two bodies for up to BATCH_MAX vectors on a (blocks, rows) grid: nothing is shared between rows, and
+// every row's last workgroup re-arms its own counters (a batch step's candidates: llama_batch.hip, nfai_hip_llama_batch_step_topk).
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t TOPK_CAND_CAP = TOPK_MAX * 64 * TOPK_NT;  // k ranges of at most 64 * TOPK_NT logits
 constexpr uint32_t TOPK_LDS_CAP = 4096;                      // heads / candidates staged in LDS (more: read from memory)
 
 struct TopkWork {  // workspace header; heads, per-wave sums and the candidate list follow (topk_work_bytes)
     uint32_t ticket, n_cand, pad[2];
-    float out_v[TOPK_MAX];     // the k largest logits, descending (ties: lower index first)
-    uint32_t out_i[TOPK_MAX];
-    float M, S;                // max_i(l_i / T), sum_i exp(l_i / T - M)
+    TopkOut out;               // the single-vector launch: the k largest logits, descending (ties: lower index first), their indices,
+                               // M = max_i(l_i / T), S = sum_i exp(l_i / T - M); the rows launch writes its callers' array instead
     float pad2[2];
 };
+static_assert(offsetof(TopkWork, out) == 16 && sizeof(TopkWork) == 16 + sizeof(TopkOut) + 8 && sizeof(TopkOut) == 8 * TOPK_MAX + 8, "workspace header");
 
 size_t topk_work_bytes(uint32_t n)
 {
     const uint32_t nw = topk_blocks(n) * (TOPK_THREADS / 64);
     return sizeof(TopkWork) + (size_t)nw * 12 + (size_t)TOPK_CAND_CAP * 8;
 }
-size_t topk_out_offset() { return offsetof(TopkWork, out_v); }
+size_t topk_out_offset() { return offsetof(TopkWork, out); }
 
 struct TopkArrays {
     float *head_v; uint32_t *head_i; float *ws; float *cand_v; uint32_t *cand_i;
@@ -333,7 +335,9 @@ __device__ __forceinline__ TopkArrays topk_arrays(TopkWork *w, uint32_t nw)
     return a;
 }
 
-__global__ __launch_bounds__(TOPK_THREADS) void k_topk_heads(const float *x, uint32_t n, TopkWork *w)
+// The two bodies see ONE vector and ONE workspace and take the range partition from gridDim.x / blockIdx.x alone: the single-vector
+// kernels call them on a 1-D grid, the rows kernels with row blockIdx.y's vector, workspace slice and output slot.
+__device__ __forceinline__ void topk_heads_body(const float *x, uint32_t n, TopkWork *w)
 {
     constexpr uint32_t WPB = TOPK_THREADS / 64;
     const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -380,7 +384,7 @@ __device__ __forceinline__ uint32_t topk_rank(const unsigned long long *keys, ui
     return rank;
 }
 
-__global__ __launch_bounds__(TOPK_THREADS) void k_topk_select(const float *x, uint32_t n, float temperature, uint32_t k, TopkWork *w)
+__device__ __forceinline__ void topk_select_body(const float *x, uint32_t n, float temperature, uint32_t k, TopkWork *w, TopkOut *out)
 {
     constexpr uint32_t WPB = TOPK_THREADS / 64;
     __shared__ __attribute__((aligned(16))) unsigned long long lk[TOPK_LDS_CAP];  // keys of the heads, later (last workgroup) of the candidates
@@ -444,7 +448,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void k_topk_select(const float *x, ui
         for (uint32_t c = threadIdx.x; c < m; c += TOPK_THREADS) {
             const unsigned long long key = lk[c];
             const uint32_t rank = topk_rank(lk, m4, key);
-            if (rank < k) { w->out_v[rank] = topk_key_value(key); w->out_i[rank] = topk_key_index(key); }
+            if (rank < k) { out->v[rank] = topk_key_value(key); out->i[rank] = topk_key_index(key); }
         }
     } else {  // thousands of equal logits around tau: correct, slow (every comparison reads memory)
         for (uint32_t c = threadIdx.x; c < m; c += TOPK_THREADS) {
@@ -454,7 +458,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void k_topk_select(const float *x, ui
             for (uint32_t j = 0; j < m && rank < k; j++)
                 rank += topk_better(__hip_atomic_load(&a.cand_v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
                                     __hip_atomic_load(&a.cand_i[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), v, i) ? 1u : 0u;
-            if (rank < k) { w->out_v[rank] = v; w->out_i[rank] = i; }
+            if (rank < k) { out->v[rank] = v; out->i[rank] = i; }
         }
     }
     // S = the waves' sums, thread-strided then a fixed tree (deterministic)
@@ -468,25 +472,64 @@ __global__ __launch_bounds__(TOPK_THREADS) void k_topk_select(const float *x, ui
         S = sv[0];
 #pragma unroll
         for (uint32_t q = 1; q < WPB; q++) S += sv[q];
-        w->M = M;
-        w->S = S;
+        out->M = M;
+        out->S = S;
         __hip_atomic_store(&w->n_cand, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm (stream-ordered with the next launch)
         __hip_atomic_store(&w->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
-hipError_t launch_topk(const float *x, uint32_t n, float temperature, uint32_t k, void *work, hipStream_t s)
+__global__ __launch_bounds__(TOPK_THREADS) void k_topk_heads(const float *x, uint32_t n, TopkWork *w) { topk_heads_body(x, n, w); }
+__global__ __launch_bounds__(TOPK_THREADS) void k_topk_select(const float *x, uint32_t n, float temperature, uint32_t k, TopkWork *w)
 {
-    if (n == 0 || k == 0 || k > TOPK_MAX || k > n || !(temperature > 0.f)) return hipErrorInvalidValue;
-    const uint32_t blocks = topk_blocks(n);
-    if ((uint64_t)blocks * TOPK_THREADS * TOPK_NT < n) return hipErrorInvalidValue;  // more logits than TOPK_BLOCKS_MAX blocks hold
+    topk_select_body(x, n, temperature, k, w, &w->out);
+}
+
+// row blockIdx.y of a batch: its own vector (a by-value pointer table, as the batched GEMVs take xs[]), its own workspace slice
+__global__ __launch_bounds__(TOPK_THREADS) void k_topk_heads_rows(TopkRowsArgs rows, uint32_t n, char *work, size_t stride)
+{
+    topk_heads_body(rows.x[blockIdx.y], n, reinterpret_cast<TopkWork *>(work + blockIdx.y * stride));
+}
+__global__ __launch_bounds__(TOPK_THREADS) void k_topk_select_rows(TopkRowsArgs rows, uint32_t n, float temperature, uint32_t k, char *work,
+                                                                   size_t stride, TopkOut *out)
+{
+    topk_select_body(rows.x[blockIdx.y], n, temperature, k, reinterpret_cast<TopkWork *>(work + blockIdx.y * stride), out + blockIdx.y);
+}
+
+// what both launch forms take; blocks: the workgroups per vector
+static bool topk_shape_ok(uint32_t n, float temperature, uint32_t k, uint32_t &blocks)
+{
+    if (n == 0 || k == 0 || k > TOPK_MAX || k > n || !(temperature > 0.f)) return false;
+    blocks = topk_blocks(n);
+    if ((uint64_t)blocks * TOPK_THREADS * TOPK_NT < n) return false;  // more logits than TOPK_BLOCKS_MAX blocks hold
     static_assert(TOPK_BLOCKS_MAX * (TOPK_THREADS / 64) <= TOPK_LDS_CAP, "the heads are ranked in LDS");
     // fewer ranges than outputs: every logit is a candidate, which the list must hold
-    if (blocks * (TOPK_THREADS / 64) < k && n > TOPK_CAND_CAP) return hipErrorInvalidValue;
+    return !(blocks * (TOPK_THREADS / 64) < k && n > TOPK_CAND_CAP);
+}
+
+hipError_t launch_topk(const float *x, uint32_t n, float temperature, uint32_t k, void *work, hipStream_t s)
+{
+    uint32_t blocks = 0;
+    if (!topk_shape_ok(n, temperature, k, blocks)) return hipErrorInvalidValue;
     k_topk_heads<<<blocks, TOPK_THREADS, 0, s>>>(x, n, reinterpret_cast<TopkWork *>(work));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     k_topk_select<<<blocks, TOPK_THREADS, 0, s>>>(x, n, temperature, k, reinterpret_cast<TopkWork *>(work));
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_rows(const TopkRowsArgs &rows, uint32_t R, uint32_t n, float temperature, uint32_t k, void *work, TopkOut *out, hipStream_t s)
+{
+    uint32_t blocks = 0;
+    if (R == 0 || R > BATCH_MAX || !work || !out || !topk_shape_ok(n, temperature, k, blocks)) return hipErrorInvalidValue;
+    for (uint32_t r = 0; r < R; r++)
+        if (!rows.x[r]) return hipErrorInvalidValue;
+    const size_t stride = topk_rows_stride(n);
+    const dim3 grid(blocks, R);
+    k_topk_heads_rows<<<grid, TOPK_THREADS, 0, s>>>(rows, n, static_cast<char *>(work), stride);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    k_topk_select_rows<<<grid, TOPK_THREADS, 0, s>>>(rows, n, temperature, k, static_cast<char *>(work), stride, out);
     return hipGetLastError();
 }
 

@@ -831,7 +831,7 @@ NFAI_API int32_t nfai_hip_llama_finalize(nfai_model_t h)
     return NFAI_OK;
 }
 
-struct TopkOut { float v[TOPK_MAX]; uint32_t i[TOPK_MAX]; float M, S; };  // the head of the top-k workspace (topk_out_offset())
+// (TopkOut, common.h: the head of the top-k workspace, topk_out_offset())
 static_assert(sizeof(TopkOut) + 16 <= 4096, "pinned staging: words 0..3 (argmax, error word, token in, spare), then the candidates");
 
 // Capture [token word H2D] -> the token -> [top-k launch] -> [argmax, error word(, candidates) D2H].  Errors inside the capture end

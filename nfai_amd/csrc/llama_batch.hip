@@ -42,6 +42,14 @@ struct Batch {
     void *d_am = nullptr, *d_attn = nullptr;
     Graph g_io[BATCH_MAX + 1];     // by column count (a batch: its n), captured on first use: [tokens H2D] -> the token -> [results D2H]
     Graph g_body;                  // a batch: the token alone (greedy)
+    // nfai_hip_llama_batch_step_topk (allocated by its first call): n workspace slices with the members' TopkOut array behind them |
+    // that array's pinned mirror | [tokens H2D] -> the token -> the two row launches -> [results + candidates D2H], captured for
+    // (topk_t, topk_k) and re-captured when they change
+    void *d_topk = nullptr;
+    TopkOut *h_topk = nullptr;
+    Graph g_topk;
+    float topk_t = 0.f;
+    uint32_t topk_k = 0;
     // column i's activation vectors: member i's own (a batch), or the window's (every column is mem[0])
     float *cx[BATCH_MAX] = {}, *ch[BATCH_MAX] = {}, *cq[BATCH_MAX] = {}, *catt[BATCH_MAX] = {}, *cact[BATCH_MAX] = {}, *clog[BATCH_MAX] = {};
     const uint32_t *d_in = nullptr;   // the step's token words (a batch: d_w->out, where the tail leaves the next step's)
@@ -322,6 +330,9 @@ void batch_free(Batch *bt)
 {
     for (Graph &g : bt->g_io) g.drop();
     bt->g_body.drop();
+    bt->g_topk.drop();
+    if (bt->d_topk) hipFree(bt->d_topk);
+    if (bt->h_topk) hipHostFree(bt->h_topk);
     if (bt->w_act) hipFree(bt->w_act);
     if (bt->d_w) hipFree(bt->d_w);
     if (bt->d_am) hipFree(bt->d_am);
@@ -608,6 +619,77 @@ NFAI_API int32_t nfai_hip_llama_batch_step(nfai_batch_t h, const uint32_t *token
         for (uint32_t i = 0; i < bt->n; i++)
             HIP_TRY(hipMemcpyAsync(logits_host + (size_t)i * V, bt->mem[i]->logits, (size_t)V * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
+    }
+    return NFAI_OK;
+}
+
+// ---- a step that returns every member's TopP candidates (the reference's DEFAULT sampler, LlamaModel.cs:128-130,165) ----------------
+namespace {
+
+TopkOut *topk_out_dev(Batch *bt) { return reinterpret_cast<TopkOut *>(static_cast<char *>(bt->d_topk) + bt->n * topk_rows_stride(bt->mem[0]->d.V)); }
+
+// [words_in] -> the token -> candidates of every member's logits (ONE pair of launches) -> [words_out + all candidates in one copy],
+// a linear chain; kept until (temperature, k) change (ensure_sync_graph in llama.hip is the single model's form).
+int ensure_topk_graph(Batch *bt, float temperature, uint32_t k)
+{
+    if (bt->g_topk && bt->topk_t == temperature && bt->topk_k == k) return NFAI_OK;
+    bt->g_topk.drop();
+    hipStream_t s = bt->ctx->stream;
+    S_TRY(capture(s, "batch top-k", [&]() -> int {
+        S_TRY(words_in(bt, s));
+        S_TRY(enqueue_batch(bt));
+        TopkRowsArgs rows;
+        for (uint32_t i = 0; i < bt->n; i++) rows.x[i] = bt->clog[i];   // fp32 logits whatever the weights are
+        const hipError_t e = launch_topk_rows(rows, bt->n, bt->mem[0]->d.V, temperature, k, bt->d_topk, topk_out_dev(bt), s);
+        if (e != hipSuccess)
+            return fail(e == hipErrorInvalidValue ? NFAI_ERR_INVALID : NFAI_ERR_HIP, "batch_step_topk: launch failed: %s", hipGetErrorString(e));
+        S_TRY(words_out(bt, s));
+        HIP_TRY(hipMemcpyAsync(bt->h_topk, topk_out_dev(bt), bt->n * sizeof(TopkOut), hipMemcpyDeviceToHost, s));
+        return NFAI_OK;
+    }, bt->g_topk));
+    bt->topk_t = temperature;
+    bt->topk_k = k;
+    return NFAI_OK;
+}
+
+}  // namespace
+
+NFAI_API int32_t nfai_hip_llama_batch_step_topk(nfai_batch_t h, const uint32_t *tokens, float temperature, uint32_t k, uint32_t *ids_out,
+                                                float *probs_out)
+{
+    BATCH_OR_FAIL(bt, h);
+    S_TRY(columns_live(bt, "batch_step_topk"));
+    // every argument is checked BEFORE anything is enqueued: a refused call leaves every member's position where it was
+    if (!tokens || !ids_out || !probs_out) return fail(NFAI_ERR_INVALID, "batch_step_topk: null argument");
+    const uint32_t V = bt->mem[0]->d.V;
+    S_TRY(tokens_ok(bt, tokens, bt->n, "batch_step_topk"));
+    if (k == 0 || k > TOPK_MAX || k > V) return fail(NFAI_ERR_INVALID, "batch_step_topk: k=%u outside [1, min(%u, V=%u)]", k, TOPK_MAX, V);
+    if (!(temperature > 0.f))
+        return fail(NFAI_ERR_INVALID, "batch_step_topk: temperature %g (the reference divides by it, SamplingUtils.cs:7)", temperature);
+    S_TRY(columns_capacity(bt, 1, "batch_step_topk"));
+    hipStream_t s = bt->ctx->stream;
+    if (!bt->d_topk) {   // (before the capture: an allocation is no stream operation)  Both or neither: a half-made pair is undone
+        void *work = nullptr;
+        TopkOut *pin = nullptr;
+        int rc = dalloc(&work, bt->n * topk_rows_stride(V) + bt->n * sizeof(TopkOut), s);
+        if (!rc && hipHostMalloc(reinterpret_cast<void **>(&pin), bt->n * sizeof(TopkOut), hipHostMallocDefault) != hipSuccess)
+            rc = fail(NFAI_ERR_OOM, "batch_step_topk: pinned staging");
+        if (rc) {
+            hipStreamSynchronize(s);
+            if (work) hipFree(work);
+            return rc;
+        }
+        bt->d_topk = work;
+        bt->h_topk = pin;
+    }
+    S_TRY(ensure_topk_graph(bt, temperature, k));
+    for (uint32_t i = 0; i < bt->n; i++) bt->h_w->in[i] = tokens[i];
+    HIP_TRY(hipGraphLaunch(bt->g_topk.exec, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    S_TRY(columns_finish(bt, nullptr, "batch_step_topk"));
+    for (uint32_t i = 0; i < bt->n; i++) {
+        const TopkOut &o = bt->h_topk[i];
+        topk_finish(o.v, o.i, o.M, o.S, temperature, k, ids_out + (size_t)i * k, probs_out + (size_t)i * k);
     }
     return NFAI_OK;
 }

@@ -410,6 +410,7 @@ class LlamaBatch:
         else:
             call("nfai_hip_llama_batch_create", hs, self.n, C.byref(h))
         self.handle = h
+        self._kw = dict(quantized=quantized, any_quant=any_quant)   # what a smaller batch over some of the members is made with
         self.V = int(self.models[0].dims["V"])
 
     def Step(self, tokens, want_logits: bool = True):
@@ -422,6 +423,91 @@ class LlamaBatch:
         call("nfai_hip_llama_batch_step", self.handle, t.ctypes.data_as(C.POINTER(C.c_uint32)),
              logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None, am.ctypes.data_as(C.POINTER(C.c_uint32)))
         return logits, am
+
+    def StepTopK(self, tokens, temperature: float = 0.5, topK: int = 40):
+        """One token per member, then every member's candidates of SamplingUtils.TopP formed on the device (SamplingUtils.cs:5-13):
+        (ids[n][topK] uint32, probs[n][topK] float32), row i what LlamaModel.StepTopK returns for member i alone.  One graph launch
+        and one synchronisation; 520 bytes per member come back instead of V floats."""
+        t = np.ascontiguousarray(tokens, np.uint32)
+        if t.size != self.n:
+            raise ValueError(f"LlamaBatch.StepTopK: {t.size} tokens for {self.n} members")
+        ids = np.empty((self.n, int(topK)), np.uint32)
+        probs = np.empty((self.n, int(topK)), np.float32)
+        call("nfai_hip_llama_batch_step_topk", self.handle, t.ctypes.data_as(C.POINTER(C.c_uint32)), float(temperature), int(topK),
+             ids.ctypes.data_as(C.POINTER(C.c_uint32)), probs.ctypes.data_as(C.POINTER(C.c_float)))
+        return ids, probs
+
+    # -- the token loop of n conversations (LlamaModel.RunAsync, :99-174, once per member)
+    def RunTokens(self, token_lists, eos: int, greedy: bool = False, max_tokens: int | None = None, rng=None):
+        """The batch counterpart of LlamaModel._run on token ids: a generator of (member, token).  token_lists[i] is member i's
+        prompt (at least one token each; another count than the batch's members is a ValueError).
+
+        Prompt phase, per member as _run does it: Ingest(tokens[:-1]) when the member has promptPrefill, else token by token; the
+        members then sit at different positions.
+        Sampling: each step feeds every running member's last token through ONE batch step.  greedy: Step(want_logits=False), the
+        token is the ArgMax.  Otherwise StepTopK, then SamplingUtils.TopPFromCandidates(ids[i], probs[i], rng=rng): exactly one draw
+        per running member per step, in ascending member order.
+        A member's stream ends as _run's does: its first token is yielded whatever it is; a later EOS is not yielded and ends the
+        stream; max_tokens counts per member; an emitted EOS is never fed.
+        Retirement: when members end, the loop goes on with a LlamaBatch over the members still running (creation is cheap) and
+        disposes the smaller batches it made.  A finished member is left exactly where its last fed token left it: nothing is
+        written behind its position and it is not stepped again.
+        A member at its KV capacity raises the library's KVCacheFull (NFAI_ERR_KV_FULL), as RunAsync of one model does."""
+        lists = [[int(t) for t in tl] for tl in token_lists]
+        if len(lists) != self.n:
+            raise ValueError(f"LlamaBatch.RunTokens: {len(lists)} prompts for {self.n} members")
+        if any(not tl for tl in lists):
+            raise ValueError("LlamaBatch.RunTokens: every member needs at least one prompt token")
+        for m, tl in zip(self.models, lists):
+            if m.promptPrefill:
+                m.Ingest(tl[:-1])
+            else:
+                for tok in tl[:-1]:
+                    m.Step(tok, want_logits=False)
+        running = list(range(self.n))            # member indices (of THIS batch) whose stream has not ended
+        last = {i: lists[i][-1] for i in running}   # the token each feeds next
+        count = {i: 0 for i in running}
+        batch, made = self, []
+        try:
+            while running:
+                toks = [last[i] for i in running]
+                if greedy:
+                    out = [int(t) for t in batch.Step(toks, want_logits=False)[1]]
+                else:
+                    ids, probs = batch.StepTopK(toks)
+                    out = [SamplingUtils.TopPFromCandidates(ids[j], probs[j], rng=rng) for j in range(len(running))]
+                still = []
+                for i, tk in zip(running, out):
+                    count[i] += 1
+                    if tk == eos and count[i] > 1:
+                        continue                 # not yielded, never fed: the member stays in front of it
+                    yield i, tk
+                    if tk != eos and (max_tokens is None or count[i] < max_tokens):
+                        last[i] = tk
+                        still.append(i)
+                if still and len(still) != len(running):
+                    batch = type(self)([self.models[i] for i in still], **self._kw)
+                    made.append(batch)
+                running = still
+        finally:
+            for b in made:
+                b.Dispose()
+
+    def RunAsync(self, prompts, greedy: bool = False, max_tokens: int | None = None, rng=None):
+        """n conversations at once: a generator of (member, text), RunTokens with member 0's tokenizer (Tokenize(prompt,
+        addBos=member.firstInput), Detokenize, EosTokenId).  The rules are RunTokens'."""
+        tok = self.models[0].tokenizer
+        if tok is None:
+            raise RuntimeError("RunAsync needs a tokenizer (nfai_amd.tokenizer.Tokenizer(metadata))")
+        prompts = list(prompts)
+        if len(prompts) != self.n:
+            raise ValueError(f"LlamaBatch.RunAsync: {len(prompts)} prompts for {self.n} members")
+        lists = []
+        for m, p in zip(self.models, prompts):
+            lists.append(tok.Tokenize(p, addBos=m.firstInput))
+            m.firstInput = False
+        for i, tk in self.RunTokens(lists, tok.EosTokenId, greedy, max_tokens, rng):
+            yield i, tok.Detokenize([tk])
 
     def Greedy(self, first_tokens, n_steps: int) -> np.ndarray:
         """n_steps tokens per member with the ArgMax fed back on the device: tokens[n_steps][n]."""

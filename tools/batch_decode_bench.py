@@ -27,6 +27,22 @@ generators), through LlamaBatch(..., quantized=True, any_quant=True) (NFAI_BATCH
 
     python tools/batch_decode_bench.py --quant q5_k_m --out profiles/batch_decode_q5_k_m.json
     python tools/batch_decode_bench.py --quant q8_0 --out profiles/batch_decode_q8_0.json
+
+--sampled: the reference's DEFAULT sampler on a batch (nfai_hip_llama_batch_step_topk) instead of the greedy comparison.  Same models
+and members, n in {1, 2, 4, 8}, positions 517-580 (64 steps per window, >= 3 windows of each form alternating, one untimed first):
+
+  step_topk_ms / step_ms    median wall time of one StepTopK call (temperature 0.5, top-40) and of one blocking
+                            Step(want_logits=False) of the same batch: what the candidate launches and the 520 bytes per member add
+  sampled batch             StepTopK, then the nucleus cut and the draw on the host per member, the drawn tokens fed back
+  sampled sequential        the same n members as single models, LlamaModel.StepTopK + the host nucleus one after another
+  logits to the host        Step(want_logits=True) of the batch, then SamplingUtils.TopP over V on the host per member: what a
+                            sampling host had to do before _batch_step_topk
+
+Aggregate tokens/s of the three (median over the windows, with their spreads) and the ratios.  Writes
+profiles/batch_sampled[_<quant>].json unless --out names another file.
+
+    python tools/batch_decode_bench.py --sampled
+    python tools/batch_decode_bench.py --sampled --quant q4_k_m
 """
 import argparse
 import json
@@ -203,6 +219,102 @@ def run_model(torch, dims, steps, windows, quant="f16"):
     return out
 
 
+def run_sampled(torch, dims, steps, windows, quant="f16"):
+    """--sampled: see the module docstring."""
+    from nfai_amd import synth
+    from nfai_amd.hip import HipBufferManager
+    from nfai_amd.llama_model import LlamaBatch, LlamaModel, SamplingUtils
+    weights = gen_weights(torch, dims, quant)
+    C = T + WARM + steps + 16
+    mgr = HipBufferManager(0)
+    dd = dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0)
+    md = synth.make_metadata(dims)
+    wt = {k: (t.data_ptr(), ty, r, c) for k, (t, ty, r, c) in weights.items()}
+    members = [LlamaModel(mgr, md, wt, C, max_batch=T, dims=dd)]
+    for _ in range(1, NMAX):
+        members.append(LlamaModel(mgr, md, wt, C, max_batch=T, dims=dd, share_from=members[0]))
+    first = []
+    for s, m in enumerate(members):
+        prompt = synth.make_tokens(dims, T, seed=99 + s)
+        prompt[0] = 128000 % dims.V
+        m.Ingest(prompt)
+        tok = int(prompt[-1])
+        for _ in range(WARM):
+            _, tok = m.Step(tok, want_logits=False)
+        first.append(tok)
+    p0 = T + WARM
+    out = {"model": dims.name, "weights": quant, "kv_cache": "f32", "positions": [p0, p0 + steps - 1], "steps_per_window": steps,
+           "temperature": 0.5, "top_k": 40, "top_p": 0.95, "by_n": {}}
+    for n in (1, 2, 4, 8):
+        ms = members[:n]
+        batch = LlamaBatch(ms, quantized=quant != "f16", any_quant=quant in ANY_QUANT)
+
+        def window(step):
+            """steps calls of step(tokens) -> next tokens, from the same positions: (seconds, seconds of every call)."""
+            for m in ms:
+                m.SetPos(p0)
+            toks, each = list(first[:n]), []
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                t1 = time.perf_counter()
+                toks = step(toks)
+                each.append(time.perf_counter() - t1)
+            return time.perf_counter() - t0, each
+
+        rng = np.random.Generator(np.random.PCG64(7))
+
+        def step_topk_only(toks):
+            ids, _ = batch.StepTopK(toks)
+            return [int(i[0]) for i in ids]
+
+        def step_only(toks):
+            return [int(t) for t in batch.Step(toks, want_logits=False)[1]]
+
+        def sampled_batch(toks):
+            ids, probs = batch.StepTopK(toks)
+            return [SamplingUtils.TopPFromCandidates(ids[i], probs[i], rng=rng) for i in range(n)]
+
+        def sampled_sequential(toks):
+            nxt = []
+            for m, tok in zip(ms, toks):
+                ids, probs = m.StepTopK(tok)
+                nxt.append(SamplingUtils.TopPFromCandidates(ids, probs, rng=rng))
+            return nxt
+
+        def logits_host(toks):
+            lg, _ = batch.Step(toks, want_logits=True)
+            return [SamplingUtils.TopP(lg[i], rng=rng) for i in range(n)]
+
+        forms = {"step_topk": step_topk_only, "step": step_only, "sampled_batch": sampled_batch,
+                 "sampled_sequential": sampled_sequential, "logits_to_host": logits_host}
+        for f in forms.values():   # untimed: graph capture, code objects
+            window(f)
+        secs = {k: [] for k in forms}
+        calls = {k: [] for k in forms}
+        for _ in range(windows):   # alternating, same positions
+            for k, f in forms.items():
+                t, each = window(f)
+                secs[k].append(t)
+                calls[k].extend(each)
+        tps = {k: [n * steps / t for t in v] for k, v in secs.items()}
+        med = {k: statistics.median(v) for k, v in tps.items()}
+        topk_ms, step_ms = statistics.median(calls["step_topk"]) * 1e3, statistics.median(calls["step"]) * 1e3
+        out["by_n"][str(n)] = {
+            "step_topk_ms": topk_ms, "step_ms": step_ms, "step_topk_over_step": topk_ms / step_ms,
+            "sampled_batch_tokens_per_s": med["sampled_batch"], "sampled_batch_spread": spread(tps["sampled_batch"]),
+            "sampled_sequential_tokens_per_s": med["sampled_sequential"], "sampled_sequential_spread": spread(tps["sampled_sequential"]),
+            "logits_to_host_tokens_per_s": med["logits_to_host"], "logits_to_host_spread": spread(tps["logits_to_host"]),
+            "speedup_over_sequential": med["sampled_batch"] / med["sampled_sequential"],
+            "speedup_over_logits_to_host": med["sampled_batch"] / med["logits_to_host"],
+            "bytes_to_host_per_step": {"step_topk": n * 520 + 36, "logits_to_host": n * dims.V * 4 + 36}}
+        batch.Dispose()
+    for m in reversed(members):
+        m.Dispose()
+    mgr.Dispose()
+    return out
+
+
 def oracle_parity(torch, dims, n=4, quant="f16"):
     """n = 4 on full-size weights at shallow staggered depths (the oracle walks every earlier token on the host): max |dlogit| over 4 steps."""
     import oracle as orc
@@ -251,11 +363,26 @@ def main():
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--only", default="", metavar="MODEL", help="one model, e.g. llama-3.2-3b")
     ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m", "q5_k_m", "q8_0"], help="weight encoding (all but f16: the int8-MFMA batch)")
+    ap.add_argument("--sampled", action="store_true", help="the default sampler on a batch (StepTopK) instead of the greedy comparison")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     from nfai_amd import synth
     torch.cuda.set_device(0)
+    if a.sampled:
+        out = {"tool": "batch_decode_bench --sampled", "weights": a.quant, "models": []}
+        for dims in (synth.LLAMA_32_3B, synth.LLAMA_32_1B):
+            if a.only and a.only != dims.name:
+                continue
+            out["models"].append(run_sampled(torch, dims, 64, max(3, a.windows), a.quant))
+            torch.cuda.empty_cache()
+        line = json.dumps(out)
+        print(line)
+        path = a.out or os.path.join(ROOT, "profiles", "batch_sampled%s.json" % ("" if a.quant == "f16" else "_" + a.quant))
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(line + "\n")
+        return
     out = {"tool": "batch_decode_bench", "weights": a.quant, "models": []}
     for dims in (synth.LLAMA_32_3B, synth.LLAMA_32_1B):
         if a.only and a.only != dims.name:
