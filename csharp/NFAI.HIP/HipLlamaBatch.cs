@@ -17,12 +17,15 @@ public sealed unsafe class HipLlamaBatch : IDisposable
     /// quantized: also admits members whose matrices are all Q4_K / Q6_K (Q4_K_M files) through nfai_hip_llama_batch_create_ex with
     /// NFAI_BATCH_QUANT: every quantised row is read and unpacked once per step and multiplied on the matrix cores for all members.
     /// anyQuant (with quantized): Q5_K and Q8_0 matrices too (Q5_K_M and Q8_0 files, NFAI_BATCH_QUANT_ANY), in any per-tensor mix.
-    public HipLlamaBatch(ReadOnlySpan<ulong> models, uint vocab, bool quantized = false, bool anyQuant = false)
+    /// wide: 1 to 16 whole fp16 models on the fp16-MFMA kernels (nfai_hip_llama_batch_create_wide); every method takes spans of Count.
+    public HipLlamaBatch(ReadOnlySpan<ulong> models, uint vocab, bool quantized = false, bool anyQuant = false, bool wide = false)
     {
         if (anyQuant && !quantized) throw new ArgumentException("anyQuant widens quantized and needs it", nameof(anyQuant));
+        if (wide && quantized) throw new ArgumentException("a wide batch takes fp16 models only", nameof(wide));
         Count = (uint)models.Length; Vocab = vocab;
         fixed (ulong* p = models)
-            Native.Check(quantized ? Native.nfai_hip_llama_batch_create_ex(p, Count, BatchQuant | (anyQuant ? BatchQuantAny : 0u), out handle)
+            Native.Check(wide ? Native.nfai_hip_llama_batch_create_wide(p, Count, 0u, out handle)
+                       : quantized ? Native.nfai_hip_llama_batch_create_ex(p, Count, BatchQuant | (anyQuant ? BatchQuantAny : 0u), out handle)
                                    : Native.nfai_hip_llama_batch_create(p, Count, out handle));
     }
 

@@ -388,6 +388,18 @@ enum nfai_batch_flags {
     NFAI_BATCH_QUANT_ANY = 1u << 2,   /* with NFAI_BATCH_QUANT: also Q5_K and Q8_0 matrices, any per-tensor mix of the four */
 };
 int32_t nfai_hip_llama_batch_create_ex(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out);
+/* ≙ up to 16 LlamaModel instances over one set of weights entering the loop LlamaModel.cs:116-125 together: the wide batch.  Every
+ * projection is MatrixMultiplyShader.cs:255-289 at M = B as in _batch_create, run on the matrix cores: a tile of 16 fp16 weight rows
+ * is the A operand of v_mfma_f32_16x16x32_f16 straight from HBM, the members' activation vectors are its 16 B columns
+ * (kernels_gemv_wide.hip).  The activations stay fp32-class: each x enters as two fp16 operands hi = half(x) and
+ * lo = half((x - hi) * 2^11), the two fp32 products are combined as hi + 2^-11 lo; |x| >= 65504 overflows, as in the prefill.
+ * n: 1 to NFAI_BATCH_WIDE_MAX members; flags must be 0.  Members are admitted as _batch_create admits them (fp16 matrices only: a
+ * quantised member is NFAI_ERR_UNSUPPORTED, naming the tensor; member 0's KV element type for all; graph-less members are admitted),
+ * with the same answers.  _batch_create and _batch_create_ex keep their limit of 8.  The handle is an ordinary batch: _batch_step,
+ * _batch_step_topk, _batch_greedy, _batch_bytes_per_token, _batch_profile_step and _batch_destroy work on it with arrays of n, and
+ * after a step every member is exactly where its own _decode_step would have left it. */
+#define NFAI_BATCH_WIDE_MAX 16
+int32_t nfai_hip_llama_batch_create_wide(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out);
 /* Frees the workspace and the graphs; the members are not touched (≙ leaving the loop LlamaModel.cs:116-125: the models live on). */
 int32_t nfai_hip_llama_batch_destroy(nfai_batch_t batch);
 /* ≙ one pass of the loop body LlamaModel.cs:116-125 for every member: tokens[i] is embedded, runs through every block at member

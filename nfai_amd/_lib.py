@@ -9,6 +9,7 @@ SO_PATH = os.environ.get("NFAI_HIP_LIB") or os.path.join(_HERE, "csrc", "libnfai
 
 OK, ERR_INVALID, ERR_HIP, ERR_OOM, ERR_KV_FULL, ERR_UNSUPPORTED, ERR_STATE = range(7)
 F32, F16, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 8, 12, 13, 14
+BATCH_WIDE_MAX = 16   # NFAI_BATCH_WIDE_MAX: members of nfai_hip_llama_batch_create_wide
 BATCH_QUANT = 1   # nfai_batch_flags: nfai_hip_llama_batch_create_ex admits Q4_K / Q6_K members
 BATCH_QUANT_ANY = 4   # with BATCH_QUANT: Q5_K and Q8_0 matrices too (bit 1 is reserved)
 LLAMA_UNFUSED, LLAMA_NO_GRAPH, LLAMA_KV_F16, LLAMA_PREFETCH, LLAMA_ENGINE = 1, 2, 4, 8, 16
@@ -119,6 +120,7 @@ SIGNATURES = {
     "nfai_hip_llama_profile_kernel": [H, u32, i32, u32, C.POINTER(f32)],
     "nfai_hip_llama_batch_create": [C.POINTER(H), u32, C.POINTER(H)],
     "nfai_hip_llama_batch_create_ex": [C.POINTER(H), u32, u32, C.POINTER(H)],
+    "nfai_hip_llama_batch_create_wide": [C.POINTER(H), u32, u32, C.POINTER(H)],
     "nfai_hip_llama_batch_destroy": [H],
     "nfai_hip_llama_batch_step": [H, C.POINTER(u32), C.POINTER(f32), C.POINTER(u32)],
     "nfai_hip_llama_batch_step_topk": [H, C.POINTER(u32), f32, u32, C.POINTER(u32), C.POINTER(f32)],

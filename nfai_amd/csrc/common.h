@@ -357,6 +357,42 @@ bool batch_gemv_kq_ok(const BatchKqArgs &a);   // shape and LDS rules of launch_
 hipError_t launch_batch_gemv_kq(const BatchKqArgs &a, hipStream_t s);
 hipError_t launch_batch_embed_kq(const void *table, int type, uint64_t n_rows, uint32_t E, const uint32_t *tok, float *const *x, uint32_t n, hipStream_t s);
 
+// ---- wide batched decode (kernels_gemv_wide.hip): up to 16 sequences per weight pass on the fp16 MFMA ------------------------------
+// The five launch forms of BatchGemvArgs with 16 columns: the weights are the MFMA's A operand, the columns its B operand (fp32 x as
+// two fp16 planes).  Columns >= n are dead.  fp16 matrices only.
+constexpr uint32_t WIDE_MAX = 16;
+static_assert(WIDE_MAX == NFAI_BATCH_WIDE_MAX, "nfai_hip.h");
+struct WideGemvArgs {
+    const void *W[3] = {nullptr, nullptr, nullptr};   // fp16 [seg_rows[i]][K]
+    uint32_t seg_rows[3] = {0, 0, 0};
+    uint32_t K = 0, n = 0;
+    int mode = 0;                      // GemvMode
+    const float *gamma = nullptr;      // RMSNorm prologue per column: every form but GEMV_RESIDUAL has it
+    float eps = 0.f;
+    const float *x[WIDE_MAX] = {};
+    float *y[WIDE_MAX] = {};
+    const float *res[WIDE_MAX] = {};
+    // GEMV_QKV_ROPE
+    void *kc[WIDE_MAX] = {}, *vc[WIDE_MAX] = {};
+    uint64_t kv_head_stride[WIDE_MAX] = {};
+    uint32_t cap[WIDE_MAX] = {};
+    const uint32_t *pos[WIDE_MAX] = {};
+    uint64_t kv_pos_stride = 0;
+    int kv_type = NFAI_F32;
+    const float *freqs = nullptr;
+    uint32_t rope_dims = 0, H = 0, Hkv = 0, D = 0;
+    uint32_t *err = nullptr;           // device word: 0x10000 | column when a column's position word is at or past its capacity
+    // GEMV_PLAIN (lm_head): first index of the maximum per column + the end-of-token bookkeeping of every member
+    void *am_work = nullptr;           // wide_argmax_bytes(), zeroed once
+    uint32_t *am_tok_batch = nullptr;  // [WIDE_MAX]: the batch's token words (next step's input)
+    uint32_t *am_tok[WIDE_MAX] = {}, *am_pos[WIDE_MAX] = {}, *am_ring[WIDE_MAX] = {};
+    uint32_t am_ring_len = 0;
+    uint32_t n_cu = 256;
+};
+constexpr size_t wide_argmax_bytes() { return (size_t)WIDE_MAX * 1024 * 8 + 256; }
+bool wide_gemv_ok(const WideGemvArgs &a);   // shape rules of launch_wide_gemv (checked by nfai_hip_llama_batch_create_wide)
+hipError_t launch_wide_gemv(const WideGemvArgs &a, hipStream_t s);
+
 // the weight-streaming engine (kernels_engine.hip): Wo + residual -> gate|up -> Wdown + residual -> next block's q|k|v, one launch
 struct EngineArgs {
     uint32_t n_ops = 3;              // 3: ends with Wdown (last block of the range); 4: + the next block's q|k|v

@@ -28,19 +28,28 @@ static_assert(offsetof(StepWords, err) == BATCH_MAX * 4 && offsetof(StepWords, n
 static_assert(offsetof(StepWords, in) == WIN_IN * 4 && offsetof(StepWords, draft) == (WIN_IN + BATCH_MAX) * 4 &&
               offsetof(StepWords, k) == (WIN_IN + 2 * BATCH_MAX) * 4, "win_ctl: BATCH_MAX drafts, then their count, behind the token words");
 static_assert(sizeof(StepWords) == offsetof(StepWords, k) + 4 && sizeof(StepWords) <= 256, "k is the last word; one 256-byte allocation");
+// A wide batch's view of the same allocation: sixteen ArgMax / token words, the error word behind them, the step's tokens at WIN_IN.
+struct WideWords {
+    uint32_t out[WIDE_MAX];
+    uint32_t err;
+    uint32_t pad[WIN_IN - WIDE_MAX - 1];
+    uint32_t in[WIDE_MAX];
+};
+static_assert(offsetof(WideWords, in) == offsetof(StepWords, in) && sizeof(WideWords) <= sizeof(StepWords), "one allocation, the tokens where a batch's are");
 
 struct Batch {
     uint32_t magic = 0x4E464254;  // 'NFBT'
     Ctx *ctx = nullptr;
     uint32_t n = 0;
-    nfai_model_t handles[BATCH_MAX] = {};
-    Model *mem[BATCH_MAX] = {};
-    uint64_t serial[BATCH_MAX] = {};
-    uint32_t gen[BATCH_MAX] = {};
+    nfai_model_t handles[WIDE_MAX] = {};
+    Model *mem[WIDE_MAX] = {};
+    uint64_t serial[WIDE_MAX] = {};
+    uint32_t gen[WIDE_MAX] = {};
+    bool wide = false;             // nfai_hip_llama_batch_create_wide: up to WIDE_MAX fp16 members on kernels_gemv_wide.hip (WideWords, WideOps)
     bool quant = false;            // the members' matrices are quantised, in the T16 layout (nfai_hip_llama_batch_create_ex, NFAI_BATCH_QUANT[_ANY])
     StepWords *d_w = nullptr, *h_w = nullptr;   // the step's words on the device | their pinned mirror
     void *d_am = nullptr, *d_attn = nullptr;
-    Graph g_io[BATCH_MAX + 1];     // by column count (a batch: its n), captured on first use: [tokens H2D] -> the token -> [results D2H]
+    Graph g_io[WIDE_MAX + 1];      // by column count (a batch: its n), captured on first use: [tokens H2D] -> the token -> [results D2H]
     Graph g_body;                  // a batch: the token alone (greedy)
     // nfai_hip_llama_batch_step_topk (allocated by its first call): n workspace slices with the members' TopkOut array behind them |
     // that array's pinned mirror | [tokens H2D] -> the token -> the two row launches -> [results + candidates D2H], captured for
@@ -51,7 +60,7 @@ struct Batch {
     float topk_t = 0.f;
     uint32_t topk_k = 0;
     // column i's activation vectors: member i's own (a batch), or the window's (every column is mem[0])
-    float *cx[BATCH_MAX] = {}, *ch[BATCH_MAX] = {}, *cq[BATCH_MAX] = {}, *catt[BATCH_MAX] = {}, *cact[BATCH_MAX] = {}, *clog[BATCH_MAX] = {};
+    float *cx[WIDE_MAX] = {}, *ch[WIDE_MAX] = {}, *cq[WIDE_MAX] = {}, *catt[WIDE_MAX] = {}, *cact[WIDE_MAX] = {}, *clog[WIDE_MAX] = {};
     const uint32_t *d_in = nullptr;   // the step's token words (a batch: d_w->out, where the tail leaves the next step's)
     // A window (nfai_hip_llama_window_create, magic 'NFWN'): up to max_tokens columns at consecutive positions of mem[0]; n is the
     // column count of the call at hand.
@@ -60,6 +69,11 @@ struct Batch {
     float *w_act = nullptr;                       // the columns' activation vectors, w_act_floats in all
     size_t w_act_floats = 0;
     uint32_t models() const { return window ? 1u : n; }   // the distinct models behind the columns
+    // the step's words in either view (w: d_w or h_w)
+    uint32_t *out_of(StepWords *w) const { return wide ? reinterpret_cast<WideWords *>(w)->out : w->out; }
+    uint32_t *in_of(StepWords *w) const { return wide ? reinterpret_cast<WideWords *>(w)->in : w->in; }
+    uint32_t *err_of(StepWords *w) const { return wide ? &reinterpret_cast<WideWords *>(w)->err : &w->err; }
+    size_t out_bytes() const { return window ? offsetof(StepWords, pad) : (wide ? offsetof(WideWords, pad) : offsetof(StepWords, n_out)); }
 };
 
 Batch *batch_of(nfai_batch_t h)
@@ -271,20 +285,151 @@ int batch_token(const BatchOps &ops, Gemv gemv, Other other)
     return gemv(KC_LMHEAD, batch_kq(ops.head(), (m0->output.ptr ? m0->output : m0->token_embd).type));
 }
 
-// One token of every column, enqueued on the stream.  timer (a profiled step): hipEvents around every launch, by class.
-int enqueue_batch(Batch *bt, LaunchTimer *timer = nullptr)
+// The launch forms of a wide batch (kernels_gemv_wide.hip): BatchOps' five GEMVs with sixteen columns, and the existing attention
+// kernel once per 8 members (`half`), each launch with its own slice of the workspace.
+struct WideOps {
+    Batch *bt;
+    WideGemvArgs base() const
+    {
+        WideGemvArgs a;
+        a.n = bt->n; a.eps = bt->mem[0]->d.eps; a.n_cu = (uint32_t)bt->ctx->prop.multiProcessorCount;
+        return a;
+    }
+    WideGemvArgs qkv(size_t l) const
+    {
+        WideGemvArgs a = base();
+        Model *m0 = bt->mem[0];
+        const nfai_llama_desc &d = m0->d;
+        const Layer &L = m0->layers[l];
+        a.W[0] = L.wq.ptr; a.W[1] = L.wk.ptr; a.W[2] = L.wv.ptr;
+        a.seg_rows[0] = (uint32_t)L.wq.rows; a.seg_rows[1] = (uint32_t)L.wk.rows; a.seg_rows[2] = (uint32_t)L.wv.rows;
+        a.K = d.E; a.mode = GEMV_QKV_ROPE; a.gamma = static_cast<const float *>(L.attn_norm.ptr);
+        for (uint32_t i = 0; i < bt->n; i++) {
+            Model *m = bt->mem[i];
+            a.x[i] = bt->cx[i]; a.y[i] = bt->cq[i];
+            a.kc[i] = m->layers[l].kcache; a.vc[i] = m->layers[l].vcache;
+            a.kv_head_stride[i] = m->kv_head_stride; a.cap[i] = m->d.C; a.pos[i] = m->d_pos;
+        }
+        a.kv_pos_stride = m0->kv_pos_stride; a.kv_type = m0->kv_f16 ? NFAI_F16 : NFAI_F32;
+        a.freqs = m0->d_freqs; a.rope_dims = d.rope_dims; a.H = d.H; a.Hkv = d.Hkv; a.D = d.D;
+        a.err = bt->err_of(bt->d_w);
+        return a;
+    }
+    BatchAttnArgs attn(size_t l, uint32_t half) const
+    {
+        BatchAttnArgs a;
+        Model *m0 = bt->mem[0];
+        const uint32_t first = half * BATCH_MAX;
+        a.n = std::min(BATCH_MAX, bt->n - first);
+        for (uint32_t i = 0; i < a.n; i++) {
+            Model *m = bt->mem[first + i];
+            a.q[i] = bt->cq[first + i]; a.o[i] = bt->catt[first + i]; a.kc[i] = m->layers[l].kcache; a.vc[i] = m->layers[l].vcache;
+            a.kv_head_stride[i] = m->kv_head_stride; a.cap[i] = m->d.C; a.pos[i] = m->d_pos;
+        }
+        a.kv_pos_stride = m0->kv_pos_stride; a.kv_type = m0->kv_f16 ? NFAI_F16 : NFAI_F32;
+        a.H = m0->d.H; a.Hkv = m0->d.Hkv; a.D = m0->d.D;
+        a.work = static_cast<char *>(bt->d_attn) + half * batch_attn_bytes(m0->d.H, m0->d.D);
+        return a;
+    }
+    WideGemvArgs wo(size_t l) const
+    {
+        WideGemvArgs a = base();
+        Model *m0 = bt->mem[0];
+        const Layer &L = m0->layers[l];
+        a.W[0] = L.wo.ptr; a.seg_rows[0] = (uint32_t)L.wo.rows; a.K = m0->d.H * m0->d.D; a.mode = GEMV_RESIDUAL;
+        for (uint32_t i = 0; i < bt->n; i++) { a.x[i] = bt->catt[i]; a.res[i] = bt->cx[i]; a.y[i] = bt->ch[i]; }
+        return a;
+    }
+    WideGemvArgs gateup(size_t l) const
+    {
+        WideGemvArgs a = base();
+        Model *m0 = bt->mem[0];
+        const Layer &L = m0->layers[l];
+        a.W[0] = L.wgate.ptr; a.W[1] = L.wup.ptr; a.seg_rows[0] = (uint32_t)L.wgate.rows; a.seg_rows[1] = (uint32_t)L.wup.rows;
+        a.K = m0->d.E; a.mode = GEMV_GATEUP; a.gamma = static_cast<const float *>(L.ffn_norm.ptr);
+        for (uint32_t i = 0; i < bt->n; i++) { a.x[i] = bt->ch[i]; a.y[i] = bt->cact[i]; }
+        return a;
+    }
+    WideGemvArgs down(size_t l) const
+    {
+        WideGemvArgs a = base();
+        Model *m0 = bt->mem[0];
+        const Layer &L = m0->layers[l];
+        a.W[0] = L.wdown.ptr; a.seg_rows[0] = (uint32_t)L.wdown.rows; a.K = m0->d.F; a.mode = GEMV_RESIDUAL;
+        for (uint32_t i = 0; i < bt->n; i++) { a.x[i] = bt->cact[i]; a.res[i] = bt->ch[i]; a.y[i] = bt->cx[i]; }
+        return a;
+    }
+    WideGemvArgs head() const
+    {
+        WideGemvArgs a = base();
+        Model *m0 = bt->mem[0];
+        const Tensor &hd = m0->output.ptr ? m0->output : m0->token_embd;  // tied when output.weight is absent (LlamaModel.cs:64-67)
+        a.W[0] = hd.ptr; a.seg_rows[0] = (uint32_t)hd.rows; a.K = m0->d.E; a.mode = GEMV_PLAIN;
+        a.gamma = static_cast<const float *>(m0->output_norm.ptr);
+        for (uint32_t i = 0; i < bt->n; i++) {
+            Model *m = bt->mem[i];
+            a.x[i] = bt->cx[i]; a.y[i] = bt->clog[i];
+            a.am_tok[i] = m->d_tok; a.am_pos[i] = m->d_pos; a.am_ring[i] = m->d_ring;
+        }
+        a.am_work = bt->d_am; a.am_tok_batch = bt->out_of(bt->d_w); a.am_ring_len = RING_LEN;
+        return a;
+    }
+};
+
+// batch_token for a wide batch: the same sequence; other(class, block, half) takes the embedding and attention launches of members
+// 8 half .. (one launch per 8 members).
+template <class Gemv, class Other>
+int wide_token(const WideOps &ops, Gemv gemv, Other other)
+{
+    Model *m0 = ops.bt->mem[0];
+    const uint32_t halves = (ops.bt->n + BATCH_MAX - 1) / BATCH_MAX;
+    for (uint32_t h = 0; h < halves; h++) S_TRY(other(KC_OTHER, (size_t)0, h));
+    for (size_t l = 0; l < m0->layers.size(); l++) {
+        S_TRY(gemv(KC_QKV, ops.qkv(l)));
+        for (uint32_t h = 0; h < halves; h++) S_TRY(other(KC_ATTN, l, h));
+        S_TRY(gemv(KC_WO, ops.wo(l)));
+        S_TRY(gemv(KC_GATEUP, ops.gateup(l)));
+        S_TRY(gemv(KC_DOWN, ops.down(l)));
+    }
+    return gemv(KC_LMHEAD, ops.head());
+}
+
+// One launch of a token, between the timer's events when the step is profiled.
+int timed_launch(LaunchTimer *timer, int c, const std::function<hipError_t()> &f)
+{
+    if (timer) S_TRY(timer->begin(c));
+    const hipError_t e = f();
+    if (e != hipSuccess)
+        return fail(e == hipErrorInvalidValue ? NFAI_ERR_INVALID : NFAI_ERR_HIP, "batch launch (class %d) failed: %s", c, hipGetErrorString(e));
+    if (timer) S_TRY(timer->end());
+    return NFAI_OK;
+}
+
+int enqueue_wide(Batch *bt, LaunchTimer *timer)
 {
     hipStream_t s = bt->ctx->stream;
     Model *m0 = bt->mem[0];
-    BatchOps ops{bt};
-    auto run = [&](int c, const std::function<hipError_t()> &f) -> int {
-        if (timer) S_TRY(timer->begin(c));
-        const hipError_t e = f();
-        if (e != hipSuccess)
-            return fail(e == hipErrorInvalidValue ? NFAI_ERR_INVALID : NFAI_ERR_HIP, "batch launch (class %d) failed: %s", c, hipGetErrorString(e));
-        if (timer) S_TRY(timer->end());
-        return NFAI_OK;
+    WideOps ops{bt};
+    auto gemv = [&](int c, const WideGemvArgs &a) { return timed_launch(timer, c, [&] { return launch_wide_gemv(a, s); }); };
+    auto other = [&](int c, size_t l, uint32_t half) {
+        return timed_launch(timer, c, [&] {
+            if (c == KC_ATTN) return launch_batch_attn(ops.attn(l, half), s);
+            const uint32_t first = half * BATCH_MAX;
+            return launch_batch_embed(m0->token_embd.ptr, m0->token_embd.rows, m0->d.E, bt->d_in + first, bt->cx + first,
+                                      std::min(BATCH_MAX, bt->n - first), s);
+        });
     };
+    return wide_token(ops, gemv, other);
+}
+
+// One token of every column, enqueued on the stream.  timer (a profiled step): hipEvents around every launch, by class.
+int enqueue_batch(Batch *bt, LaunchTimer *timer = nullptr)
+{
+    if (bt->wide) return enqueue_wide(bt, timer);
+    hipStream_t s = bt->ctx->stream;
+    Model *m0 = bt->mem[0];
+    BatchOps ops{bt};
+    auto run = [&](int c, const std::function<hipError_t()> &f) { return timed_launch(timer, c, f); };
     float *xs[BATCH_MAX] = {};
     for (uint32_t i = 0; i < bt->n; i++) xs[i] = bt->cx[i];
     auto gemv = [&](int c, const BatchKqArgs &k) { return run(c, [&] { return bt->quant ? launch_batch_gemv_kq(k, s) : launch_batch_gemv(k, s); }); };
@@ -303,13 +448,13 @@ int enqueue_batch(Batch *bt, LaunchTimer *timer = nullptr)
 int words_in(Batch *bt, hipStream_t s)
 {
     if (bt->window) HIP_TRY(hipMemcpyAsync(bt->d_w->in, bt->h_w->in, sizeof(StepWords) - offsetof(StepWords, in), hipMemcpyHostToDevice, s));
-    else HIP_TRY(hipMemcpyAsync(bt->d_w->out, bt->h_w->in, bt->n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    else HIP_TRY(hipMemcpyAsync(bt->out_of(bt->d_w), bt->in_of(bt->h_w), bt->n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     return NFAI_OK;
 }
 
 int words_out(Batch *bt, hipStream_t s)
 {
-    HIP_TRY(hipMemcpyAsync(bt->h_w, bt->d_w, bt->window ? offsetof(StepWords, pad) : offsetof(StepWords, n_out), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(bt->h_w, bt->d_w, bt->out_bytes(), hipMemcpyDeviceToHost, s));
     return NFAI_OK;
 }
 
@@ -349,9 +494,9 @@ int columns_device_failed(Batch *bt, uint32_t code, const char *fn)
 {
     hipStream_t s = bt->ctx->stream;
     for (uint32_t i = 0; i < bt->models(); i++) HIP_TRY(hipMemcpyAsync(bt->mem[i]->d_pos, &bt->mem[i]->pos_host, 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(&bt->d_w->err, 0, 4, s));
+    HIP_TRY(hipMemsetAsync(bt->err_of(bt->d_w), 0, 4, s));
     HIP_TRY(hipStreamSynchronize(s));
-    bt->h_w->err = 0;
+    *bt->err_of(bt->h_w) = 0;
     const uint32_t i = code & 0xFFu;
     if (bt->window)
         return fail(NFAI_ERR_KV_FULL, "%s: column %u: the position word on the device put it at or past the KV capacity %u (code 0x%x); the "
@@ -364,7 +509,7 @@ int columns_device_failed(Batch *bt, uint32_t code, const char *fn)
 // one token per member; a window: the emitted count, *n_out).
 int columns_finish(Batch *bt, uint32_t *n_out, const char *fn)
 {
-    if (bt->h_w->err) return columns_device_failed(bt, bt->h_w->err, fn);
+    if (*bt->err_of(bt->h_w)) return columns_device_failed(bt, *bt->err_of(bt->h_w), fn);
     if (!bt->window) {
         for (uint32_t i = 0; i < bt->n; i++) { bt->mem[i]->pos_host++; bt->mem[i]->x_last = bt->mem[i]->x; }
         return NFAI_OK;
@@ -477,6 +622,12 @@ bool shapes_ok(Batch *bt, uint32_t win_tokens, uint32_t &t_bad)
     bt->d_w = &words; bt->d_am = &dummy; bt->d_attn = &dummy;   // placeholders for the argument checks only
     const uint32_t n = bt->n;
     bool ok = attn_group_ok(m0->d.H / m0->d.Hkv);
+    if (bt->wide) {
+        ok = ok && wide_token(WideOps{bt}, [](int, const WideGemvArgs &a) { return wide_gemv_ok(a) ? 0 : 1; }, [](int, size_t, uint32_t) { return 0; }) == 0;
+        bt->d_w = nullptr; bt->d_am = nullptr; bt->d_attn = nullptr;
+        t_bad = n;
+        return ok;
+    }
     t_bad = n;
     for (uint32_t t = win_tokens ? 1 : n; ok && t <= (win_tokens ? win_tokens : n); t++) {
         bt->n = t_bad = t;
@@ -498,8 +649,9 @@ int columns_alloc(Batch *bt, uint32_t win_tokens, const char *fn)
     Model *m0 = bt->mem[0];
     hipStream_t s = bt->ctx->stream;
     S_TRY(dalloc(reinterpret_cast<void **>(&bt->d_w), sizeof(StepWords), s));
-    S_TRY(dalloc(&bt->d_am, batch_argmax_bytes(), s));
-    S_TRY(dalloc(&bt->d_attn, win_tokens ? window_attn_bytes(m0->d.H, m0->d.D) : batch_attn_bytes(m0->d.H, m0->d.D), s));
+    S_TRY(dalloc(&bt->d_am, bt->wide ? wide_argmax_bytes() : batch_argmax_bytes(), s));
+    // (a wide batch: one workspace slice per attention launch of 8 members)
+    S_TRY(dalloc(&bt->d_attn, win_tokens ? window_attn_bytes(m0->d.H, m0->d.D) : (bt->wide ? 2 : 1) * batch_attn_bytes(m0->d.H, m0->d.D), s));
     if (win_tokens) {
         const nfai_llama_desc &d = m0->d;
         auto r64 = [](size_t v) { return (v + 63) & ~(size_t)63; };   // every vector on a 256-byte boundary
@@ -514,7 +666,7 @@ int columns_alloc(Batch *bt, uint32_t win_tokens, const char *fn)
     }
     if (hipHostMalloc(reinterpret_cast<void **>(&bt->h_w), sizeof(StepWords), hipHostMallocDefault) != hipSuccess) return fail(NFAI_ERR_OOM, "%s: pinned staging", fn);
     memset(bt->h_w, 0, sizeof(StepWords));
-    bt->d_in = win_tokens ? bt->d_w->in : bt->d_w->out;
+    bt->d_in = win_tokens ? bt->d_w->in : bt->out_of(bt->d_w);
     if (hipStreamSynchronize(s) != hipSuccess) return fail(NFAI_ERR_HIP, "%s: stream synchronisation failed", fn);
     return NFAI_OK;
 }
@@ -524,16 +676,20 @@ int columns_alloc(Batch *bt, uint32_t win_tokens, const char *fn)
 // fn: the entry point's name in messages.  flags: NFAI_BATCH_* (0 = the fp16 batch of nfai_hip_llama_batch_create).
 // win_tokens > 0 (nfai_hip_llama_window_create, n = 1): the one model is admitted as a batch admits a member, and the object made is a
 // window of win_tokens columns over it.
-static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out, const char *fn, uint32_t win_tokens = 0)
+// wide (nfai_hip_llama_batch_create_wide): up to WIDE_MAX fp16 members on the MFMA kernels; flags must be 0.
+static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out, const char *fn, uint32_t win_tokens = 0,
+                             bool wide = false)
 {
     if (!models || !out) return fail(NFAI_ERR_INVALID, "%s: null argument", fn);
+    if (wide && flags) return fail(NFAI_ERR_INVALID, "%s: invalid flags 0x%x (a wide batch takes none: fp16 matrices only)", fn, flags);
+    if (wide && (n < 1 || n > WIDE_MAX)) return fail(NFAI_ERR_INVALID, "%s: invalid n = %u (a wide batch holds 1 to %u models)", fn, n, WIDE_MAX);
     if (flags & ~(uint32_t)(NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY))
         return fail(NFAI_ERR_INVALID, "%s: invalid flags 0x%x (known: NFAI_BATCH_QUANT = 0x%x, NFAI_BATCH_QUANT_ANY = 0x%x)", fn, flags,
                     NFAI_BATCH_QUANT, NFAI_BATCH_QUANT_ANY);
     if ((flags & NFAI_BATCH_QUANT_ANY) && !(flags & NFAI_BATCH_QUANT))
         return fail(NFAI_ERR_INVALID, "%s: flags 0x%x: NFAI_BATCH_QUANT_ANY widens NFAI_BATCH_QUANT and is only valid together with it", fn, flags);
-    if (n < 1 || n > BATCH_MAX) return fail(NFAI_ERR_INVALID, "%s: invalid n = %u (a batch holds 1 to %u models)", fn, n, BATCH_MAX);
-    Model *mem[BATCH_MAX] = {};
+    if (!wide && (n < 1 || n > BATCH_MAX)) return fail(NFAI_ERR_INVALID, "%s: invalid n = %u (a batch holds 1 to %u models)", fn, n, BATCH_MAX);
+    Model *mem[WIDE_MAX] = {};
     for (uint32_t i = 0; i < n; i++) {
         mem[i] = model_of(models[i]);
         if (!mem[i]) return fail(NFAI_ERR_INVALID, "%s: member %u: invalid model handle", fn, i);
@@ -551,6 +707,7 @@ static int batch_create_impl(const nfai_model_t *models, uint32_t n, uint32_t fl
     bt->ctx = m0->ctx;
     bt->n = n;
     bt->quant = quant;
+    bt->wide = wide;
     for (uint32_t i = 0; i < n; i++) {
         Model *m = mem[i];
         bt->handles[i] = models[i]; bt->mem[i] = m; bt->serial[i] = m->serial; bt->gen[i] = m->weights_gen;
@@ -590,6 +747,11 @@ NFAI_API int32_t nfai_hip_llama_batch_create_ex(const nfai_model_t *models, uint
     return batch_create_impl(models, n, flags, out, "batch_create_ex");
 }
 
+NFAI_API int32_t nfai_hip_llama_batch_create_wide(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out)
+{
+    return batch_create_impl(models, n, flags, out, "batch_create_wide", 0, true);
+}
+
 NFAI_API int32_t nfai_hip_llama_batch_destroy(nfai_batch_t h)
 {
     BATCH_OR_FAIL(bt, h);
@@ -608,12 +770,12 @@ NFAI_API int32_t nfai_hip_llama_batch_step(nfai_batch_t h, const uint32_t *token
     S_TRY(columns_capacity(bt, 1, "batch_step"));
     S_TRY(columns_capture(bt, true, bt->g_io[bt->n]));
     hipStream_t s = bt->ctx->stream;
-    for (uint32_t i = 0; i < bt->n; i++) bt->h_w->in[i] = tokens[i];
+    for (uint32_t i = 0; i < bt->n; i++) bt->in_of(bt->h_w)[i] = tokens[i];
     HIP_TRY(hipGraphLaunch(bt->g_io[bt->n].exec, s));
     HIP_TRY(hipStreamSynchronize(s));
     S_TRY(columns_finish(bt, nullptr, "batch_step"));
     if (argmax)
-        for (uint32_t i = 0; i < bt->n; i++) argmax[i] = bt->h_w->out[i];
+        for (uint32_t i = 0; i < bt->n; i++) argmax[i] = bt->out_of(bt->h_w)[i];
     if (logits_host) {
         const uint32_t V = bt->mem[0]->d.V;
         for (uint32_t i = 0; i < bt->n; i++)
@@ -638,11 +800,16 @@ int ensure_topk_graph(Batch *bt, float temperature, uint32_t k)
     S_TRY(capture(s, "batch top-k", [&]() -> int {
         S_TRY(words_in(bt, s));
         S_TRY(enqueue_batch(bt));
-        TopkRowsArgs rows;
-        for (uint32_t i = 0; i < bt->n; i++) rows.x[i] = bt->clog[i];   // fp32 logits whatever the weights are
-        const hipError_t e = launch_topk_rows(rows, bt->n, bt->mem[0]->d.V, temperature, k, bt->d_topk, topk_out_dev(bt), s);
-        if (e != hipSuccess)
-            return fail(e == hipErrorInvalidValue ? NFAI_ERR_INVALID : NFAI_ERR_HIP, "batch_step_topk: launch failed: %s", hipGetErrorString(e));
+        const uint32_t V = bt->mem[0]->d.V;
+        for (uint32_t first = 0; first < bt->n; first += BATCH_MAX) {   // one pair of launches per 8 rows (a wide batch: two)
+            TopkRowsArgs rows;
+            const uint32_t r = std::min(BATCH_MAX, bt->n - first);
+            for (uint32_t i = 0; i < r; i++) rows.x[i] = bt->clog[first + i];   // fp32 logits whatever the weights are
+            const hipError_t e = launch_topk_rows(rows, r, V, temperature, k, static_cast<char *>(bt->d_topk) + first * topk_rows_stride(V),
+                                                  topk_out_dev(bt) + first, s);
+            if (e != hipSuccess)
+                return fail(e == hipErrorInvalidValue ? NFAI_ERR_INVALID : NFAI_ERR_HIP, "batch_step_topk: launch failed: %s", hipGetErrorString(e));
+        }
         S_TRY(words_out(bt, s));
         HIP_TRY(hipMemcpyAsync(bt->h_topk, topk_out_dev(bt), bt->n * sizeof(TopkOut), hipMemcpyDeviceToHost, s));
         return NFAI_OK;
@@ -683,7 +850,7 @@ NFAI_API int32_t nfai_hip_llama_batch_step_topk(nfai_batch_t h, const uint32_t *
         bt->h_topk = pin;
     }
     S_TRY(ensure_topk_graph(bt, temperature, k));
-    for (uint32_t i = 0; i < bt->n; i++) bt->h_w->in[i] = tokens[i];
+    for (uint32_t i = 0; i < bt->n; i++) bt->in_of(bt->h_w)[i] = tokens[i];
     HIP_TRY(hipGraphLaunch(bt->g_topk.exec, s));
     HIP_TRY(hipStreamSynchronize(s));
     S_TRY(columns_finish(bt, nullptr, "batch_step_topk"));
@@ -704,7 +871,7 @@ NFAI_API int32_t nfai_hip_llama_batch_greedy(nfai_batch_t h, const uint32_t *fir
     S_TRY(columns_capacity(bt, n_steps, "batch_greedy"));
     S_TRY(columns_capture(bt, false, bt->g_body));
     hipStream_t s = bt->ctx->stream;
-    for (uint32_t i = 0; i < bt->n; i++) bt->h_w->in[i] = first_tokens[i];
+    for (uint32_t i = 0; i < bt->n; i++) bt->in_of(bt->h_w)[i] = first_tokens[i];
     S_TRY(words_in(bt, s));
     // the feedback stays on the device: the lm_head launch leaves every member's ArgMax in the batch's token words
     for (uint32_t st = 0; st < n_steps; st++) HIP_TRY(hipGraphLaunch(bt->g_body.exec, s));
@@ -713,7 +880,7 @@ NFAI_API int32_t nfai_hip_llama_batch_greedy(nfai_batch_t h, const uint32_t *fir
         HIP_TRY(hipMemcpyAsync(ring.data() + (size_t)i * RING_LEN, bt->mem[i]->d_ring, RING_LEN * 4, hipMemcpyDeviceToHost, s));
     S_TRY(words_out(bt, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (bt->h_w->err) return columns_device_failed(bt, bt->h_w->err, "batch_greedy");
+    if (*bt->err_of(bt->h_w)) return columns_device_failed(bt, *bt->err_of(bt->h_w), "batch_greedy");
     for (uint32_t i = 0; i < bt->n; i++) {
         Model *m = bt->mem[i];
         for (uint32_t st = 0; st < n_steps; st++) tokens_out[(size_t)st * bt->n + i] = ring[(size_t)i * RING_LEN + (m->pos_host + st) % RING_LEN];
@@ -748,7 +915,7 @@ NFAI_API int32_t nfai_hip_llama_batch_profile_step(nfai_batch_t h, const uint32_
     if (!tokens || !ms_by_class || !launches_by_class) return fail(NFAI_ERR_INVALID, "batch_profile_step: null argument");
     S_TRY(tokens_ok(bt, tokens, bt->n, "batch_profile_step"));
     S_TRY(columns_capacity(bt, 1, "batch_profile_step"));
-    for (uint32_t i = 0; i < bt->n; i++) bt->h_w->in[i] = tokens[i];
+    for (uint32_t i = 0; i < bt->n; i++) bt->in_of(bt->h_w)[i] = tokens[i];
     return profile_columns(bt, ms_by_class, launches_by_class, "batch_profile_step");
 }
 

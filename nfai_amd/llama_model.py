@@ -396,21 +396,27 @@ class LlamaBatch:
     1 to 8 whole models whose matrices are all Q4_K / Q6_K; with any_quant=True besides it: Q5_K and Q8_0 matrices too, in any
     per-tensor mix of the four) on one buffer manager,
     one of them the donor of the others (`share_from`).  Each member keeps its own KV cache and position and stays a normal
-    LlamaModel: Step / Ingest / SetPos on a member between batch steps are seen by the next batch step."""
+    LlamaModel: Step / Ingest / SetPos on a member between batch steps are seen by the next batch step.
+    wide=True: 1 to 16 whole fp16 models on the fp16-MFMA kernels (nfai_hip_llama_batch_create_wide); every method works on it with
+    lists of n, and RunTokens / RunAsync keep the batches they re-form on retirement wide."""
 
-    def __init__(self, models, quantized: bool = False, any_quant: bool = False):
+    def __init__(self, models, quantized: bool = False, any_quant: bool = False, wide: bool = False):
         if any_quant and not quantized:
             raise ValueError("LlamaBatch: any_quant=True widens quantized=True and needs it")
+        if wide and quantized:
+            raise ValueError("LlamaBatch: wide=True takes fp16 models only")
         self.models = list(models)
         self.n = len(self.models)
         hs = (_lib.H * max(self.n, 1))(*[m.handle.value if isinstance(m.handle, _lib.H) else int(m.handle) for m in self.models])
         h = _lib.H()
-        if quantized:   # also admits members whose matrices are all Q4_K / Q6_K (Q4_K_M files): the int8-MFMA batch
+        if wide:
+            call("nfai_hip_llama_batch_create_wide", hs, self.n, 0, C.byref(h))
+        elif quantized:   # also admits members whose matrices are all Q4_K / Q6_K (Q4_K_M files): the int8-MFMA batch
             call("nfai_hip_llama_batch_create_ex", hs, self.n, _lib.BATCH_QUANT | (_lib.BATCH_QUANT_ANY if any_quant else 0), C.byref(h))
         else:
             call("nfai_hip_llama_batch_create", hs, self.n, C.byref(h))
         self.handle = h
-        self._kw = dict(quantized=quantized, any_quant=any_quant)   # what a smaller batch over some of the members is made with
+        self._kw = dict(quantized=quantized, any_quant=any_quant, wide=wide)   # what a smaller batch over some of the members is made with
         self.V = int(self.models[0].dims["V"])
 
     def Step(self, tokens, want_logits: bool = True):
@@ -438,7 +444,7 @@ class LlamaBatch:
         return ids, probs
 
     # -- the token loop of n conversations (LlamaModel.RunAsync, :99-174, once per member)
-    def RunTokens(self, token_lists, eos: int, greedy: bool = False, max_tokens: int | None = None, rng=None):
+    def RunTokens(self, token_lists, eos: int, greedy: bool = False, max_tokens: int | None = None, rng=None, wide: bool | None = None):
         """The batch counterpart of LlamaModel._run on token ids: a generator of (member, token).  token_lists[i] is member i's
         prompt (at least one token each; another count than the batch's members is a ValueError).
 
@@ -452,7 +458,9 @@ class LlamaBatch:
         Retirement: when members end, the loop goes on with a LlamaBatch over the members still running (creation is cheap) and
         disposes the smaller batches it made.  A finished member is left exactly where its last fed token left it: nothing is
         written behind its position and it is not stepped again.
-        A member at its KV capacity raises the library's KVCacheFull (NFAI_ERR_KV_FULL), as RunAsync of one model does."""
+        A member at its KV capacity raises the library's KVCacheFull (NFAI_ERR_KV_FULL), as RunAsync of one model does.
+        wide: whether the batches re-formed on retirement are wide ones (None: as this batch is)."""
+        kw = dict(self._kw) if wide is None else dict(self._kw, wide=bool(wide))
         lists = [[int(t) for t in tl] for tl in token_lists]
         if len(lists) != self.n:
             raise ValueError(f"LlamaBatch.RunTokens: {len(lists)} prompts for {self.n} members")
@@ -486,14 +494,14 @@ class LlamaBatch:
                         last[i] = tk
                         still.append(i)
                 if still and len(still) != len(running):
-                    batch = type(self)([self.models[i] for i in still], **self._kw)
+                    batch = type(self)([self.models[i] for i in still], **kw)
                     made.append(batch)
                 running = still
         finally:
             for b in made:
                 b.Dispose()
 
-    def RunAsync(self, prompts, greedy: bool = False, max_tokens: int | None = None, rng=None):
+    def RunAsync(self, prompts, greedy: bool = False, max_tokens: int | None = None, rng=None, wide: bool | None = None):
         """n conversations at once: a generator of (member, text), RunTokens with member 0's tokenizer (Tokenize(prompt,
         addBos=member.firstInput), Detokenize, EosTokenId).  The rules are RunTokens'."""
         tok = self.models[0].tokenizer
@@ -506,7 +514,7 @@ class LlamaBatch:
         for m, p in zip(self.models, prompts):
             lists.append(tok.Tokenize(p, addBos=m.firstInput))
             m.firstInput = False
-        for i, tk in self.RunTokens(lists, tok.EosTokenId, greedy, max_tokens, rng):
+        for i, tk in self.RunTokens(lists, tok.EosTokenId, greedy, max_tokens, rng, wide):
             yield i, tok.Detokenize([tk])
 
     def Greedy(self, first_tokens, n_steps: int) -> np.ndarray:

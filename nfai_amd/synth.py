@@ -63,6 +63,11 @@ TINY_D128 = LlamaDims("tiny-llama-d128", 512, 3, 4, 2, 128, 1024, 768, False)
 # F = 8192 gives gate|up and Wdown the wide forms and the K splits; (H + 2 Hkv) D = 1920 is a multiple of 80 and of 48.
 THIN_F8192 = LlamaDims("thin-f8192", 256, 2, 4, 2, 64, 8192, 512, True)
 THIN_H9 = LlamaDims("thin-h9-d128", 256, 2, 9, 3, 128, 512, 512, True)
+# Thin one-block models at the K-panel edges of the wide batched decode (kernels_gemv_wide.hip stages x in panels of 2048 k;
+# tests/test_gpu_batch_wide.py): E = 3072 is one and a half panels (RMSNorm across them), E = 4096 two, F = 14336 seven.
+THIN_E3072 = LlamaDims("thin-e3072", 3072, 1, 4, 2, 64, 512, 512, True)
+THIN_E4096 = LlamaDims("thin-e4096", 4096, 1, 4, 2, 64, 512, 512, True)
+THIN_F14336 = LlamaDims("thin-f14336", 256, 1, 4, 2, 64, 14336, 512, True)
 
 BY_NAME ={d.name: d for d in (LLAMA_32_1B, LLAMA_32_3B, LLAMA_31_8B, TINY, TINY_D128)}
 

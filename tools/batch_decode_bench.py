@@ -43,6 +43,16 @@ profiles/batch_sampled[_<quant>].json unless --out names another file.
 
     python tools/batch_decode_bench.py --sampled
     python tools/batch_decode_bench.py --sampled --quant q4_k_m
+
+--wide: the wide batch (nfai_hip_llama_batch_create_wide, LlamaBatch(..., wide=True); fp16 only) against the existing one.  16 members
+prepared as above; the same windows and alternation over seven forms: n = 8 through the existing batch, n = 8 / 12 / 16 through the
+wide one, and the same 8 / 12 / 16 members stepped sequentially.  Per form ms per step and aggregate tokens/s (median, the windows,
+max - min); the bar: wide n = 16 exceeds the EXISTING path's n = 8 aggregate tokens/s by more than the two figures' spreads added
+(wide n = 8 against existing n = 8 is recorded beside it).  Plus _batch_profile_step per class at n = 16, and parity in the run: wide
+n = 16 against the members' own _decode_step at depth, and against the CPU oracle at 1B.  Writes profiles/batch_decode_wide.json
+unless --out names another file.
+
+    python tools/batch_decode_bench.py --wide
 """
 import argparse
 import json
@@ -315,7 +325,135 @@ def run_sampled(torch, dims, steps, windows, quant="f16"):
     return out
 
 
-def oracle_parity(torch, dims, n=4, quant="f16"):
+def run_wide(torch, dims, steps, windows):
+    """--wide: see the module docstring."""
+    from nfai_amd import synth
+    from nfai_amd.hip import HipBufferManager
+    from nfai_amd.llama_model import LlamaBatch, LlamaModel
+    NW = 16
+    weights = gen_weights(torch, dims, "f16")
+    C = T + WARM + steps + 16
+    mgr = HipBufferManager(0)
+    dd = dict(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, eps=1e-5, rope_dims=dims.D, rope_base=500000.0)
+    md = synth.make_metadata(dims)
+    wt = {k: (t.data_ptr(), ty, r, c) for k, (t, ty, r, c) in weights.items()}
+    members = [LlamaModel(mgr, md, wt, C, max_batch=T, dims=dd)]
+    for _ in range(1, NW):
+        members.append(LlamaModel(mgr, md, wt, C, max_batch=T, dims=dd, share_from=members[0]))
+    first = []
+    for s, m in enumerate(members):
+        prompt = synth.make_tokens(dims, T, seed=99 + s)
+        prompt[0] = 128000 % dims.V
+        m.Ingest(prompt)
+        tok = int(prompt[-1])
+        for _ in range(WARM):
+            _, tok = m.Step(tok, want_logits=False)
+        first.append(tok)
+    p0 = T + WARM
+
+    def rewind(ms):
+        for m in ms:
+            m.SetPos(p0)
+
+    def batch_form(batch, n):
+        def window():
+            rewind(members[:n])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            batch.Greedy(first[:n], steps)
+            return time.perf_counter() - t0
+        return window
+
+    def seq_form(n):
+        def window():
+            rewind(members[:n])
+            for m, tok in zip(members[:n], first):
+                m.SetToken(tok)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                for m in members[:n]:
+                    m.Enqueue(1)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+        return window
+
+    batches = {"batch_8": (LlamaBatch(members[:8]), 8), "wide_8": (LlamaBatch(members[:8], wide=True), 8),
+               "wide_12": (LlamaBatch(members[:12], wide=True), 12), "wide_16": (LlamaBatch(members, wide=True), 16)}
+    forms = {k: (batch_form(b, n), n) for k, (b, n) in batches.items()}
+    forms.update({f"sequential_{n}": (seq_form(n), n) for n in (8, 12, 16)})
+    for f, _ in forms.values():   # untimed: graph capture, code objects, every shape of the window
+        f()
+    secs = {k: [] for k in forms}
+    for _ in range(windows):      # alternating, same positions
+        for k, (f, _) in forms.items():
+            secs[k].append(f())
+    out = {"model": dims.name, "weights": "f16", "kv_cache": "f32", "positions": [p0, p0 + steps - 1], "steps_per_window": steps, "forms": {}}
+    for k, (_, n) in forms.items():
+        tps = [n * steps / t for t in secs[k]]
+        out["forms"][k] = {"n": n, "ms_per_step": statistics.median(secs[k]) / steps * 1e3, "tokens_per_s": statistics.median(tps),
+                           "windows_tokens_per_s": tps, "spread_tokens_per_s": max(tps) - min(tps), "spread": spread(tps)}
+    fm = out["forms"]
+    for n in (8, 12, 16):
+        fm[f"wide_{n}"]["speedup_over_sequential"] = fm[f"wide_{n}"]["tokens_per_s"] / fm[f"sequential_{n}"]["tokens_per_s"]
+    gain = fm["wide_16"]["tokens_per_s"] - fm["batch_8"]["tokens_per_s"]
+    out["bar"] = {"wide_16_over_batch_8": fm["wide_16"]["tokens_per_s"] / fm["batch_8"]["tokens_per_s"],
+                  "wide_8_over_batch_8": fm["wide_8"]["tokens_per_s"] / fm["batch_8"]["tokens_per_s"],
+                  "gain_tokens_per_s": gain, "spreads_added_tokens_per_s": fm["wide_16"]["spread_tokens_per_s"] + fm["batch_8"]["spread_tokens_per_s"],
+                  "met": gain > fm["wide_16"]["spread_tokens_per_s"] + fm["batch_8"]["spread_tokens_per_s"]}
+    # the byte model and the launch classes at n = 16
+    w16 = batches["wide_16"][0]
+    for m in members:
+        m.SetPos(p0 + steps // 2)
+    bytes16 = w16.BytesPerToken()
+    for m in members[:8]:
+        m.SetPos(p0 + steps // 2)
+    bytes8 = batches["batch_8"][0].BytesPerToken()
+    out["bytes_per_step"] = {"wide_16": bytes16, "batch_8": bytes8}
+    out["step_frac_of_8TBps"] = {"wide_16": bytes16 / (fm["wide_16"]["ms_per_step"] * 1e-3) / HBM_PEAK,
+                                 "batch_8": bytes8 / (fm["batch_8"]["ms_per_step"] * 1e-3) / HBM_PEAK}
+    classes = {}
+    for key, n in (("wide_16", 16), ("batch_8", 8)):
+        b = batches[key][0]
+        rewind(members[:n])
+        b.ProfileStep(first[:n])   # eager, one step (it advances the members)
+        prof = b.ProfileStep(first[:n])
+        cb = class_bytes(weights, dims, [p0 + 1] * n)
+        classes[key] = {}
+        for c in CLASSES:
+            ms_c, launches = prof[c]
+            if launches:
+                us = ms_c * 1e3 / launches
+                classes[key][c] = {"us_per_launch": us, "launches_per_step": launches, "us_per_step": ms_c * 1e3, "bytes_per_launch": int(cb[c]),
+                                   "frac_hbm_roofline": cb[c] / HBM_PEAK / (us * 1e-6) if us > 0 else None}
+    out["kernel_classes"] = classes
+    # wide n = 16 against the members' own decode path at depth, 4 positions
+    rewind(members)
+    solo = []
+    for i, m in enumerate(members):
+        tok, rows = first[i], []
+        for _ in range(4):
+            lg, tok = m.Step(tok)
+            rows.append(lg)
+        solo.append(rows)
+    rewind(members)
+    cur, worst, top = list(first), 0.0, 0.0
+    for p in range(4):
+        lg, am = w16.Step(cur)
+        for i in range(NW):
+            worst = max(worst, float(np.abs(lg[i] - solo[i][p]).max()))
+            top = max(top, float(np.abs(solo[i][p]).max()))
+        cur = [int(np.argmax(solo[i][p])) for i in range(NW)]
+    out["parity_vs_decode_step_at_depth"] = {"n": NW, "positions": [p0, p0 + 3], "max_abs_logit_diff": worst, "max_abs_logit": top}
+    for b, _ in batches.values():
+        b.Dispose()
+    for m in reversed(members):
+        m.Dispose()
+    mgr.Dispose()
+    return out
+
+
+def oracle_parity(torch, dims, n=4, quant="f16", wide=False):
     """n = 4 on full-size weights at shallow staggered depths (the oracle walks every earlier token on the host): max |dlogit| over 4 steps."""
     import oracle as orc
     from nfai_amd import synth
@@ -335,14 +473,14 @@ def oracle_parity(torch, dims, n=4, quant="f16"):
     refs = []
     for s in range(n):
         ref = orc.OracleLlama(orc.LlamaDesc(E=dims.E, L=dims.L, H=dims.H, Hkv=dims.Hkv, D=dims.D, F=dims.F, V=dims.V, C=C), host)
-        for t in toks[s][:2 + 3 * s]:
+        for t in toks[s][:2 + (s if wide else 3 * s)]:
             ms[s].Step(int(t), want_logits=False)
             ref.step(int(t), want_logits=False)
         refs.append(ref)
-    batch = LlamaBatch(ms, quantized=quant != "f16", any_quant=quant in ANY_QUANT)
+    batch = LlamaBatch(ms, wide=True) if wide else LlamaBatch(ms, quantized=quant != "f16", any_quant=quant in ANY_QUANT)
     worst, top, same = 0.0, 0.0, []
     for i in range(4):
-        st = [int(toks[s][2 + 3 * s + i]) for s in range(n)]
+        st = [int(toks[s][2 + (s if wide else 3 * s) + i]) for s in range(n)]
         lg, am = batch.Step(st)
         for s in range(n):
             want = refs[s].step(st[s])
@@ -364,11 +502,30 @@ def main():
     ap.add_argument("--only", default="", metavar="MODEL", help="one model, e.g. llama-3.2-3b")
     ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m", "q5_k_m", "q8_0"], help="weight encoding (all but f16: the int8-MFMA batch)")
     ap.add_argument("--sampled", action="store_true", help="the default sampler on a batch (StepTopK) instead of the greedy comparison")
+    ap.add_argument("--wide", action="store_true", help="the wide batch (up to 16 members, fp16 MFMA) against the existing one")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     from nfai_amd import synth
     torch.cuda.set_device(0)
+    if a.wide:
+        if a.quant != "f16":
+            ap.error("--wide takes fp16 weights only")
+        out = {"tool": "batch_decode_bench --wide", "weights": "f16", "models": []}
+        for dims in (synth.LLAMA_32_3B, synth.LLAMA_32_1B):
+            if a.only and a.only != dims.name:
+                continue
+            out["models"].append(run_wide(torch, dims, a.steps, max(3, a.windows)))
+            torch.cuda.empty_cache()
+        if not a.no_check:
+            out["parity_vs_oracle"] = oracle_parity(torch, synth.LLAMA_32_1B, n=16, wide=True)
+        line = json.dumps(out)
+        print(line)
+        path = a.out or os.path.join(ROOT, "profiles", "batch_decode_wide.json")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(line + "\n")
+        return
     if a.sampled:
         out = {"tool": "batch_decode_bench --sampled", "weights": a.quant, "models": []}
         for dims in (synth.LLAMA_32_3B, synth.LLAMA_32_1B):
