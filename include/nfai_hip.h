@@ -392,7 +392,8 @@ int32_t nfai_hip_llama_batch_create_ex(const nfai_model_t *models, uint32_t n, u
  * projection is MatrixMultiplyShader.cs:255-289 at M = B as in _batch_create, run on the matrix cores: a tile of 16 fp16 weight rows
  * is the A operand of v_mfma_f32_16x16x32_f16 straight from HBM, the members' activation vectors are its 16 B columns
  * (kernels_gemv_wide.hip).  The activations stay fp32-class: each x enters as two fp16 operands hi = half(x) and
- * lo = half((x - hi) * 2^11), the two fp32 products are combined as hi + 2^-11 lo; |x| >= 65504 overflows, as in the prefill.
+ * lo = half((x - hi) * 2^11), the two fp32 products are combined as hi + 2^-11 lo; |x| >= 65504 overflows, as in the prefill
+ * (tested: activations from 2^-17 of the synthetic models' up to 32768 and subnormal fp16 weights, which the MFMA takes at full value).
  * n: 1 to NFAI_BATCH_WIDE_MAX members; flags must be 0.  Members are admitted as _batch_create admits them (fp16 matrices only: a
  * quantised member is NFAI_ERR_UNSUPPORTED, naming the tensor; member 0's KV element type for all; graph-less members are admitted),
  * with the same answers.  _batch_create and _batch_create_ex keep their limit of 8.  The handle is an ordinary batch: _batch_step,

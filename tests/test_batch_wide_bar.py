@@ -44,30 +44,39 @@ def gemv(W32, x, with_lo):
 class Restated:
     """One sequence through the model, float32 throughout, every matrix product through gemv()."""
 
-    def __init__(self, d, w, with_lo):
+    def __init__(self, d, w, with_lo, cap=CAP):
         self.d, self.with_lo = d, with_lo
         self.w = {k: np.asarray(v, np.float32) for k, v in w.items()}
         self.freqs = npo.rope_freqs(d.D).astype(np.float32)
-        self.K = [np.zeros((CAP, d.Hkv * d.D), np.float32) for _ in range(d.L)]
-        self.V = [np.zeros((CAP, d.Hkv * d.D), np.float32) for _ in range(d.L)]
+        self.K = [np.zeros((cap, d.Hkv * d.D), np.float32) for _ in range(d.L)]
+        self.V = [np.zeros((cap, d.Hkv * d.D), np.float32) for _ in range(d.L)]
         self.pos = 0
+
+    def mm(self, name, x):
+        """Every matrix product of the model (tests/scale_models.py records its inputs and restates it in other ways)."""
+        return gemv(self.w[name], x, self.with_lo)
+
+    def row(self, kind, v):
+        """The q ("q"), K ("k") or V ("v") row as the attention reads it (tests/scale_models.py rounds them to fp16)."""
+        return v
 
     def step(self, tok, eps=1e-5):
         d, w, p, f32 = self.d, self.w, self.pos, np.float32
-        mm = lambda name, x: gemv(w[name], x, self.with_lo)
+        mm, row = self.mm, self.row
         x = w["token_embd.weight"][tok].copy()
         for l in range(d.L):
             b = f"blk.{l}."
             xn = npo.rmsnorm(x, w[b + "attn_norm.weight"], eps).astype(f32)
-            q = npo.rope(mm(b + "attn_q.weight", xn), self.freqs, d.D, d.H, d.D, p).astype(f32)
-            self.K[l][p] = npo.rope(mm(b + "attn_k.weight", xn), self.freqs, d.D, d.Hkv, d.D, p).astype(f32)
-            self.V[l][p] = mm(b + "attn_v.weight", xn)
+            q = row("q", npo.rope(mm(b + "attn_q.weight", xn), self.freqs, d.D, d.H, d.D, p).astype(f32))
+            self.K[l][p] = row("k", npo.rope(mm(b + "attn_k.weight", xn), self.freqs, d.D, d.Hkv, d.D, p).astype(f32))
+            self.V[l][p] = row("v", mm(b + "attn_v.weight", xn))
             att = npo.attention(q, self.K[l], self.V[l], d.H, d.Hkv, d.D, p + 1).astype(f32)
             h = (x + mm(b + "attn_output.weight", att)).astype(f32)
             hn = npo.rmsnorm(h, w[b + "ffn_norm.weight"], eps).astype(f32)
             act = (mm(b + "ffn_up.weight", hn) * npo.silu(mm(b + "ffn_gate.weight", hn)).astype(f32)).astype(f32)
             x = (h + mm(b + "ffn_down.weight", act)).astype(f32)
         xn = npo.rmsnorm(x, w["output_norm.weight"], eps).astype(f32)
+        self.x = x
         self.pos += 1
         return mm("output.weight" if "output.weight" in w else "token_embd.weight", xn)
 
