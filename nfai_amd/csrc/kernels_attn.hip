@@ -20,7 +20,7 @@
 //      ticket (the op-level entry, small devices, NFAI_ATTN_POLL=0): every partial word is stored write-through, each storing
 //        wave drains its stores, the block's barrier, ONE lane takes a ticket with an agent-scope atomic; the block whose
 //        ticket is last reloads the partials and merges (guide, visibility table row 1).
-//  - k_attn_wo (below): the same program in four waves of a workgroup whose other four waves stream Wo into registers
+//  - k_attn_wo (below): the same program in the first workgroups of a launch whose other workgroups stream Wo into registers
 //    meanwhile and apply it to the merged output: attention + Wo + residual in one launch.
 // The number of ACTIVE slices depends on the sequence length, which is read from device memory so
 // a captured hipGraph can be replayed for every position; inactive blocks exit at once.
@@ -61,8 +61,7 @@ struct AttnParams {
     const float *wo_res;     // residual [E]
     float *wo_y;             // [E]
     uint32_t E, HD, nbw;     // Wo rows, row length, workgroups that share the rows
-    uint32_t wo_lds_off;     // byte offset of the Wo waves' LDS region (after the attention waves')
-    uint32_t wo_delay;       // x 64 clocks between launch start and the Wo waves' weight requests (workgroups that run a slice)
+    uint32_t wo_delay;       // x 64 clocks between a Wo workgroup's start and its weight requests
     uint32_t withhold;       // test hook (AttnArgs::debug_withhold)
     NFAI_STAMP_PARAM
 };
@@ -132,8 +131,7 @@ __device__ __forceinline__ void publish(uint64_t *g, uint32_t tag, float v)
 }
 
 // The attention waves' program.  PUB: the merged output is also published as {value, tag} granules (p.att_gran) for the Wo waves of
-// the fused launch; every path through the body executes three workgroup barriers and, when the context has more than one slice,
-// a fourth (k_attn_wo's Wo waves execute the same number).
+// the fused launch.
 template <int LPP, int G, bool F16, bool ONLINE, bool POLL, bool PUB>
 __device__ __forceinline__ void attn_body(const AttnParams &p, const uint32_t kvh, const uint32_t split)
 {
@@ -555,14 +553,17 @@ __global__ __launch_bounds__(ATTN_BLOCK) void k_attn_decode(const AttnParams p)
 }
 
 // ---- attention + Wo in one launch ------------------------------------------------------------------------------------------
-// Workgroup = four attention waves (the program above, kv head = id % Hkv, slice = id / Hkv) + four Wo waves.  The Wo waves
-// request their share of Wo (rows id*E/nbw ..., R rows x U KiB per wave, straight to registers, non-temporal) and the residual at
-// the START of the launch, so the weight stream overlaps the whole attention; then they take part in the attention waves'
-// workgroup barriers (raw s_barrier: no drain of the loads in flight), poll the merged attention output — {value, tag}
-// granules published by the blocks of the last slices — into LDS, meet on an LDS counter and finish with R x U dot products
-// per lane from registers.  Saves one kernel boundary and the Wo launch's own first-byte latency per block (TransformerBlock.cs:
-// 144-161 in one launch).  Every poll is bounded; a poll that gives up sets the error word and the Wo waves store nothing.
-constexpr uint32_t WO_WAVES = 4;
+// One launch of 256-thread workgroups with two programs.  Workgroups [0, Hkv x max_split) run the attention program above (kv head =
+// id % Hkv, slice = id / Hkv: exactly what k_attn_decode runs, with its own workgroup barriers, plus the merged output published as
+// {value, tag} granules).  Workgroups [Hkv x max_split, Hkv x max_split + nbw) are four Wo waves each: they request their share of
+// Wo (rows w*E/nbw ..., R rows x U KiB per wave, straight to registers, non-temporal) and the residual near the START of the launch,
+// so the weight stream overlaps the whole attention; then they poll the merged attention output into LDS, meet on LDS arrival words
+// and finish with R x U dot products per lane from registers.  The two roles exchange data only through the tagged granules in
+// global memory and share no workgroup, so no Wo wave takes part in a barrier of the attention program (when they shared one, the
+// slice's waves sat at their first barrier until the Wo waves had pushed their weight requests: scores in LDS 1 us late).  Saves one
+// kernel boundary and the Wo launch's own first-byte latency per block (TransformerBlock.cs:144-161 in one launch).  Every poll is
+// bounded; a poll that gives up sets the error word and the Wo waves store nothing.
+constexpr uint32_t WO_WAVES = ATTN_BLOCK / 64;
 
 __device__ __forceinline__ uint32_t wo_xs_index(uint32_t k)  // the activation layout of kernels_gemv.hip (fp16 weights)
 {
@@ -571,42 +572,35 @@ __device__ __forceinline__ uint32_t wo_xs_index(uint32_t k)  // the activation l
 }
 
 template <int LPP, int G, bool F16, int R, int U>
-__global__ __launch_bounds__(ATTN_BLOCK + WO_WAVES * 64) void k_attn_wo(const AttnParams p)
+__global__ __launch_bounds__(ATTN_BLOCK) void k_attn_wo(const AttnParams p)
 {
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t kvh = blockIdx.x % p.Hkv, split = blockIdx.x / p.Hkv;
-    if (wave < ATTN_BLOCK / 64) {
-        if (split < p.max_split) attn_body<LPP, G, F16, false, true, true>(p, kvh, split);
+    const uint32_t natt = p.Hkv * p.max_split;
+    if (blockIdx.x < natt) {
+        attn_body<LPP, G, F16, false, true, true>(p, blockIdx.x % p.Hkv, blockIdx.x / p.Hkv);
         return;
     }
-    // ---- Wo waves ----------------------------------------------------------------------------------------------------------
-    if (blockIdx.x >= p.nbw) return;
+    // ---- Wo workgroups -----------------------------------------------------------------------------------------------------
+    const uint32_t wb = blockIdx.x - natt;
     typedef __attribute__((address_space(1))) uint8_t g_u8;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *xs = reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(smem) + p.wo_lds_off);  // HD floats, permuted
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(xs + p.HD);                                     // one arrival word per Wo wave
-    const uint32_t ww = wave - ATTN_BLOCK / 64, lane = threadIdx.x & 63;
-    const uint32_t rb = (uint32_t)(((uint64_t)p.E * blockIdx.x) / p.nbw), re = (uint32_t)(((uint64_t)p.E * (blockIdx.x + 1)) / p.nbw);
+    float *xs = smem;                                          // HD floats, permuted
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(xs + p.HD);  // one arrival word per Wo wave
+    const uint32_t ww = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const uint32_t rb = (uint32_t)(((uint64_t)p.E * wb) / p.nbw), re = (uint32_t)(((uint64_t)p.E * (wb + 1)) / p.nbw);
     STAMP_DECL;
     STAMP(0);
 #ifdef NFAI_STAMPS
-    const uint32_t stamp_wave = p.Hkv * p.max_split * (ATTN_BLOCK / 64) + blockIdx.x * WO_WAVES + ww;  // behind the attention waves' rows
+    const uint32_t stamp_wave = (natt + wb) * WO_WAVES + ww;  // behind the attention waves' rows
 #endif
-    // (1) the weights and the residual, requested a little after the slice's own K and V rows (below); then the attention waves'
-    //     barriers: three per active slice, a fourth when there is more than one slice (see attn_body).
-    uint32_t nsplit, chunk;
-    attn_split(p.pos[0] + 1, p.min_chunk, p.max_split, nsplit, chunk);
-    const bool has_slice = split < nsplit;
-    // this wave's arrival word is cleared BEFORE a workgroup barrier and read by the others only after it: LDS keeps what an
-    // earlier launch left there, and another model's launch may have left this very tag
+    // (1) this wave's arrival word is cleared BEFORE the barrier of the four Wo waves below and read by the others only after it: LDS
+    //     keeps what an earlier launch left there, and another model's launch may have left this very tag
     if (lane == 0) __hip_atomic_store(&cnt[ww], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    // A CU's memory requests are served in order.  Requested at once, 18 KB of weights per wave sit in front of the slice's K and V
-    // rows; requested after the slice's first barrier (scores in LDS, 3 us in) the stream is still arriving when the slice
-    // publishes and the polls of the hand-off queue behind it.  Measured optimum (3B, positions 520-647; tokens/s): no delay 626,
-    // 0.8 us 624, 1.3 us 631, 1.6 us 631, 1.9 us 628, 2.3 us 624, 3.2 us 613, after barrier 1: 618 (two launches: 621).
-    if (has_slice)
-        for (uint32_t i = 0; i < p.wo_delay; i++) __builtin_amdgcn_s_sleep(1);  // 64 clocks each
+    // (2) the weights and the residual.  A CU's memory requests are served in order, and a Wo workgroup cannot know whether its CU
+    //     also hosts a slice: requested at once, 18 KB of weights per wave sit in front of that slice's K and V rows; requested late,
+    //     the stream is still arriving when the merged output is due.  NFAI_ATTN_WO_DELAY, x 64 clocks; tokens/s at 3B, positions
+    //     520-647, three runs each: no delay 692, 0.7 us 703, 1.4 us 694 (0.35-1.1 us on a second box: 693-695, flat).
+    for (uint32_t i = 0; i < p.wo_delay; i++) __builtin_amdgcn_s_sleep(1);  // 64 clocks each
     asm volatile("" ::: "memory");
     u32x4 w[R][U];
 #pragma unroll
@@ -619,19 +613,26 @@ __global__ __launch_bounds__(ATTN_BLOCK + WO_WAVES * 64) void k_attn_wo(const At
     const float e = ((const __attribute__((address_space(1))) float *)p.wo_res)[min(rb + ww * R + min(lane, (uint32_t)R - 1), p.E - 1)];
     asm volatile("" ::: "memory");
     STAMP(1);  // weights requested
-    __builtin_amdgcn_s_barrier();  // slice: barrier 1 of the attention waves; no slice: those waves end without a barrier
-    if (has_slice) {
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_s_barrier();
-        if (nsplit > 1) __builtin_amdgcn_s_barrier();
-    }
-    STAMP(2);  // the attention waves of this workgroup are done with barriers
-    // (3) the attention output: this wave's quarter of the HD granules, 16-byte sc1 loads (two granules), until every tag matches
+    __builtin_amdgcn_s_barrier();  // the four Wo waves alone (raw: no drain of the loads in flight): every arrival word is cleared
+    STAMP(2);  // arrival words cleared in the whole workgroup
+    // (3) the attention output.  First ONE lane watches one 16-byte word (two granules) of this wave's quarter, so that the Wo
+    //     workgroups, which get here long before the slices publish, do not sweep the whole vector across the XCDs over and over;
+    //     then the wave's quarter of the HD granules, 16-byte sc1 loads, until every tag matches (correctness rests on this sweep)
     const uint32_t tag = p.epoch[0] * p.tag_mul + p.tag_add;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.att_gran, 0, (int)(p.HD * 8), 0x00020000);
+    uint32_t spins = 0;
+    for (; spins < ATTN_SPIN_CAP; spins++) {
+        uint32_t hit = 0;
+        if (lane == 0) {
+            const u32x4 s = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(((ww * U + U - 1) * 64 + 63) * 16), 0, 16));
+            hit = s[1] == tag && s[3] == tag;
+        }
+        if (__builtin_amdgcn_readfirstlane(hit)) break;
+        __builtin_amdgcn_s_sleep(4);
+    }
     u32x4 v[U];
     bool ok = false;
-    for (uint32_t spins = 0; spins < ATTN_SPIN_CAP; spins++) {
+    do {  // (at least one sweep, also when the watch above gave up)
 #pragma unroll
         for (int u = 0; u < U; u++) v[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(((ww * U + u) * 64 + lane) * 16), 0, 16));
         ok = true;
@@ -639,7 +640,7 @@ __global__ __launch_bounds__(ATTN_BLOCK + WO_WAVES * 64) void k_attn_wo(const At
         for (int u = 0; u < U; u++) ok = ok && v[u][1] == tag && v[u][3] == tag;
         if (__all(ok)) break;
         __builtin_amdgcn_s_sleep(1);
-    }
+    } while (++spins < ATTN_SPIN_CAP);
     const bool good = __all(ok);
     STAMP(3);  // this wave's quarter of the attention output seen
 #pragma unroll
@@ -648,13 +649,13 @@ __global__ __launch_bounds__(ATTN_BLOCK + WO_WAVES * 64) void k_attn_wo(const At
         const uint32_t k = (((ww * U + u) * 64 + lane) * 2);
         *reinterpret_cast<f32x2 *>(xs + wo_xs_index(k)) = f32x2{vf[0], vf[2]};  // k is even: the pair stays adjacent under the permutation
     }
-    // (4) the four Wo waves meet on LDS words (the attention waves are done with barriers, some have ended): word ww = this launch's
-    //     tag once wave ww's quarter is in LDS (tag + 1: its poll gave up)
+    // (4) the four Wo waves meet on LDS words: word ww = this launch's tag once wave ww's quarter is in LDS (tag + 1: its poll gave
+    //     up), a bounded wait like every other in this launch
     if (lane == 0) {
         if (!good && p.err) __hip_atomic_fetch_or(p.err, 0x2000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(&cnt[ww], good ? tag : tag + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
-    for (uint32_t spins = 0;; spins++) {
+    for (uint32_t meet = 0;; meet++) {
         uint32_t seen = 0, bad = 0;
 #pragma unroll
         for (uint32_t i = 0; i < WO_WAVES; i++) {
@@ -664,7 +665,7 @@ __global__ __launch_bounds__(ATTN_BLOCK + WO_WAVES * 64) void k_attn_wo(const At
         }
         if (bad) return;
         if (seen == WO_WAVES) break;
-        if (spins > (1u << 22)) {
+        if (meet > (1u << 22)) {
             if (lane == 0 && p.err) __hip_atomic_fetch_or(p.err, 0x4000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
         }
@@ -896,15 +897,15 @@ static bool attn_wo_plan(const AttnArgs &a, const GemvArgs &g, uint32_t &nbw, At
 template <int LPP, int G, int R, int U>
 static bool resident_aw(bool f16, uint32_t nblocks, size_t lds, uint32_t n_cu)
 {
-    return f16 ? grid_resident(k_attn_wo<LPP, G, true, R, U>, ATTN_BLOCK + WO_WAVES * 64, lds, nblocks, n_cu)
-               : grid_resident(k_attn_wo<LPP, G, false, R, U>, ATTN_BLOCK + WO_WAVES * 64, lds, nblocks, n_cu);
+    return f16 ? grid_resident(k_attn_wo<LPP, G, true, R, U>, ATTN_BLOCK, lds, nblocks, n_cu)
+               : grid_resident(k_attn_wo<LPP, G, false, R, U>, ATTN_BLOCK, lds, nblocks, n_cu);
 }
 
 template <int LPP, int G, int R, int U>
 static hipError_t launch_aw(const AttnParams &p, bool f16, uint32_t nblocks, size_t lds, hipStream_t s)
 {
-    if (f16) hipLaunchKernelGGL((k_attn_wo<LPP, G, true, R, U>), dim3(nblocks), dim3(ATTN_BLOCK + WO_WAVES * 64), lds, s, p);
-    else hipLaunchKernelGGL((k_attn_wo<LPP, G, false, R, U>), dim3(nblocks), dim3(ATTN_BLOCK + WO_WAVES * 64), lds, s, p);
+    if (f16) hipLaunchKernelGGL((k_attn_wo<LPP, G, true, R, U>), dim3(nblocks), dim3(ATTN_BLOCK), lds, s, p);
+    else hipLaunchKernelGGL((k_attn_wo<LPP, G, false, R, U>), dim3(nblocks), dim3(ATTN_BLOCK), lds, s, p);
     return hipGetLastError();
 }
 
@@ -922,11 +923,14 @@ static bool attn_wo_prepare(const AttnArgs &a, const GemvArgs &g, AttnParams &p,
     p.att_gran = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(a.partials) + attn_partials_bytes(a.H, a.Hkv, a.D, true));
     p.wo = static_cast<const uint8_t *>(g.W[0]); p.wo_res = g.res; p.wo_y = g.y;
     p.E = g.seg_rows[0]; p.HD = HD; p.nbw = nbw;
-    static const int env_delay = getenv("NFAI_ATTN_WO_DELAY") ? atoi(getenv("NFAI_ATTN_WO_DELAY")) : 54;  // x 64 clocks = 1.4 us
-    p.wo_delay = env_delay >= 0 && env_delay < 4096 ? (uint32_t)env_delay : 54;
-    p.wo_lds_off = (uint32_t)((lds + 15) & ~(size_t)15);
-    nblocks = a.Hkv * p.max_split > nbw ? a.Hkv * p.max_split : nbw;
-    lds = p.wo_lds_off + ((size_t)HD + 16) * sizeof(float);
+    static const int env_delay = getenv("NFAI_ATTN_WO_DELAY") ? atoi(getenv("NFAI_ATTN_WO_DELAY")) : 27;  // x 64 clocks = 0.7 us
+    p.wo_delay = env_delay >= 0 && env_delay < 4096 ? (uint32_t)env_delay : 27;
+    // the attention workgroups come first and keep their ids (a kv head's slices share an XCD: workgroups are dealt round-robin over
+    // the eight), the Wo workgroups follow from a multiple of eight
+    if (a.Hkv * p.max_split % 8) return false;
+    nblocks = a.Hkv * p.max_split + nbw;
+    const size_t wo_lds = ((size_t)HD + 16) * sizeof(float);  // a workgroup runs ONE of the two programs: the larger need, not the sum
+    if (wo_lds > lds) lds = wo_lds;
     if (lds > 64 * 1024) return false;
     // every workgroup of this launch waits for others: the whole grid must be resident at once (occupancy query of the kernel itself)
     const bool f16 = a.kv_type == NFAI_F16;
@@ -953,7 +957,7 @@ hipError_t launch_attn_wo(const AttnArgs &a, const GemvArgs &g, hipStream_t s)
     size_t lds;
     if (!attn_wo_prepare(a, g, p, sh, nblocks, lds)) return hipErrorInvalidValue;
     const bool f16 = a.kv_type == NFAI_F16;
-    NFAI_STAMP_SET(p, "attn_wo", nblocks, ATTN_BLOCK + WO_WAVES * 64);
+    NFAI_STAMP_SET(p, "attn_wo", nblocks, ATTN_BLOCK);
     if (sh.lpp == 32 && sh.G == 3) return launch_aw<32, 3, 3, 6>(p, f16, nblocks, lds, s);
     if (sh.lpp == 32 && sh.G == 4) return launch_aw<32, 4, 4, 8>(p, f16, nblocks, lds, s);
     if (sh.lpp == 16 && sh.G == 4) return launch_aw<16, 4, 2, 4>(p, f16, nblocks, lds, s);

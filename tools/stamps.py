@@ -197,7 +197,7 @@ def main():
             a_ = a_[~np.isnan(a_)]
             return (pct(a_) + [round(float(a_.max()), 3)]) if a_.size else None
         an = ["start", "K, V, q requested", "scores in LDS", "softmax done", "own granules issued", "all granules of the share seen, merge weights in LDS", "-", "share of the merged output published"]
-        wn = ["start", "weights requested", "attention waves of the workgroup done with barriers", "quarter of the attention output seen",
+        wn = ["start", "weights requested", "arrival words cleared in the workgroup", "quarter of the attention output seen",
               "all four quarters in LDS", "multiplied, reduced, stores issued", "stores acknowledged"]
         out["attn_wo"] = {"what": "fused attention + Wo launch: time of each event since the launch's first stamp, us, [median, p10, p90, max] over the waves of the role, all blocks' launches of one token",
                           "span_us": pct(aw["span"]),
