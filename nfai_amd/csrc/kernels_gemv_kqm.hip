@@ -17,7 +17,7 @@
 // signed base-256 digits; sum q * x' = S0 + 256 S1 + 65536 S2 is exact in int32, the K-quant scales
 // (d * sc, dmin * m, the -32 offset of Q6_K via the group sums of x') are applied in fp32 exactly
 // as ggml defines the block; Q8_0 (d * q, q a signed byte) needs neither sums nor offsets: one d per lane
-// and MFMA.  The only approximation is x' = round(x * 2^S): 24 bits relative to
+// and MFMA; Q4_0 (d * (q - 8), q a nibble) takes Q4_K's staging and sums of x' with d and 8 d in place of the scale and the min.  The only approximation is x' = round(x * 2^S): 24 bits relative to
 // the largest |x| of the super-block.  Against the fp32 oracle the differences are at the level of
 // fp32 summation-order noise (tests/test_gpu_kquant.py states the tolerance; max |dlogit| 1.5e-5 at 3B).
 //
@@ -127,12 +127,13 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
     // the blocks); the activations are staged in both fragment layouts and every step branches on its segment's type.
     // QT = NFAI_Q8_0_T16: its own A-fragment layout, never mixed with the K-quants (llama.hip gives a Q8_0 segment its own launch).
     // QT = NFAI_Q5_K_T16: the Q4_K staging (fragments and sums of x'); NFAI_KQ_MIXED5: Q5_K and Q6_K segments as NFAI_KQ_MIXED.
-    constexpr bool HAS8 = QT == NFAI_Q8_0_T16, HAS5 = QT == NFAI_Q5_K_T16 || QT == NFAI_KQ_MIXED5;
-    constexpr bool HAS4 = !HAS8 && QT != NFAI_Q6_K_T16, HAS6 = !HAS8 && QT != NFAI_Q4_K_T16 && QT != NFAI_Q5_K_T16, MIXED = HAS4 && HAS6;
+    // QT = NFAI_Q4_0_T16: the Q4_K staging too (t16.h); launched on Q4_0 segments only (llama.hip gives them their own launch).
+    constexpr bool HAS8 = QT == NFAI_Q8_0_T16, HAS5 = QT == NFAI_Q5_K_T16 || QT == NFAI_KQ_MIXED5, IS40 = QT == NFAI_Q4_0_T16;
+    constexpr bool HAS4 = !HAS8 && QT != NFAI_Q6_K_T16, HAS6 = !HAS8 && !IS40 && QT != NFAI_Q4_K_T16 && QT != NFAI_Q5_K_T16, MIXED = HAS4 && HAS6;
     static_assert(!MIXED || MODE == GEMV_QKV_ROPE, "mixed encodings exist for the q|k|v launch only");
     using Regs = typename std::conditional<
         QT == NFAI_Q4_K_T16, Q4T,
-        typename std::conditional<HAS8, Q8T, typename std::conditional<QT == NFAI_Q5_K_T16, Q5T, Q6T>::type>::type>::type;
+        typename std::conditional<HAS8, Q8T, typename std::conditional<QT == NFAI_Q5_K_T16, Q5T, typename std::conditional<IS40, Q40T, Q6T>::type>::type>::type>::type;
     constexpr int R = MODE == GEMV_GATEUP ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x, lane = tid & 63, nw = blockDim.x >> 6;
@@ -200,6 +201,8 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
             buf = q8t_load(p, seg, tile, blk, lane);
         } else if constexpr (QT == NFAI_Q5_K_T16) {
             buf = q5t_load(p, seg, tile, blk, lane);
+        } else if constexpr (IS40) {
+            buf = q40t_load(p, seg, tile, blk, lane);
         } else {
             if ((p.seg6 >> seg) & 1u) {
                 buf = q6t_load(p, seg, tile, blk, lane);
@@ -294,6 +297,7 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
                     const f32x4 sm = *reinterpret_cast<const f32x4 *>(sums + (blk * 4 + g) * 4);
                     if constexpr (QT == NFAI_Q4_K_T16) a = q4t_dot(buf, af, f32x2{sm[0], sm[1]}, g);
                     else if constexpr (QT == NFAI_Q5_K_T16) a = q5t_dot(buf, af, f32x2{sm[0], sm[1]}, g);
+                    else if constexpr (IS40) a = q40t_dot(buf, af, f32x2{sm[0], sm[1]});
                     else if constexpr (HAS5) a = q5t_dot(Q5T{buf.qla, buf.qlb, buf.sc, u32x2{buf.qh[0], buf.qh[1]}}, af, f32x2{sm[0], sm[1]}, g);
                     else a = q4t_dot(Q4T{buf.qla, buf.qlb, buf.sc}, af, f32x2{sm[0], sm[1]}, g);
                 }
@@ -467,6 +471,24 @@ __global__ void k_repack_q80_t16(const uint8_t *src, uint8_t *dst, uint32_t n_ti
     }
 }
 
+// ---- Q4_0 repack: native 18-byte blocks (row-major: d, qs[16]) -> T16 planes (same bytes) ---------------------------------
+__global__ void k_repack_q40_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
+{
+    const uint64_t tb = blockIdx.x;
+    const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB), t = threadIdx.x;
+    const uint64_t nblk = t16_nblk(n_tiles, NB);
+    // native blocks are only 2-byte aligned: byte copies
+    for (uint32_t e = t; e < 2048; e += blockDim.x) {
+        const uint32_t h = e >> 10, ln = (e >> 4) & 63, b = e & 15, G = ln >> 4, r = ln & 15;
+        const uint8_t *s = src + ((uint64_t)(tile * 16 + r) * NB * 8 + blk * 8 + 2 * G + h) * GGML_Q4_0_BLOCK;
+        t16_q40_qs(dst, tb)[e] = s[2 + b];
+    }
+    for (uint32_t e = t; e < 256; e += blockDim.x) {
+        const uint32_t r = e >> 4, b32 = (e & 15) >> 1;  // half b32 of the row = d of 32-block b32
+        t16_q40_d(dst, nblk, tb)[e] = src[((uint64_t)(tile * 16 + r) * NB * 8 + blk * 8 + b32) * GGML_Q4_0_BLOCK + (e & 1)];
+    }
+}
+
 // ---- Q5_K repack: native 176-byte blocks (row-major: d, dmin, scales[12], qh[32], qs[128]) -> T16 planes -------------------
 // Planes 0 and 1 as k_repack_q4k_t16 (qs at byte 48 of the block, the header is its first 16 bytes); plane 2: the bit order of t16.h.
 __global__ void k_repack_q5k_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
@@ -510,6 +532,10 @@ hipError_t launch_repack_q80_t16(const void *native, void *tiled, uint64_t rows,
 hipError_t launch_repack_q5k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
 {
     return launch_repack_t16(k_repack_q5k_t16, 256, native, tiled, rows, cols, s);
+}
+hipError_t launch_repack_q40_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
+{
+    return launch_repack_t16(k_repack_q40_t16, 256, native, tiled, rows, cols, s);
 }
 
 // ---- rows of a T16 table -> fp32 (embedding gather): row tok[t] to y + t * E (prefill, single token) or, y == nullptr, to x[t] (the
@@ -606,6 +632,23 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
                 *reinterpret_cast<f16x8 *>(orow + sb * 32 + c * 8) = o;
             }
         }
+    } else if constexpr (QT == NFAI_Q4_0_T16) {
+        const uint32_t dw = *reinterpret_cast<const uint32_t *>(t16_q40_d(W, nblk, tb) + r * 16 + g * 4);
+#pragma unroll
+        for (int h = 0; h < 2; h++) {  // 32-block 2g + h of row r: weights 0..15 = low nibbles, 16..31 = high nibbles of its 16 bytes
+            const u32x4 q = load_nt16(t16_q40_qs(W, tb) + h * 1024 + lane * 16);
+            const float d = h ? h2f_hi(dw) : h2f_lo(dw);
+#pragma unroll
+            for (int c = 0; c < 4; c++) {  // 8 weights: nibble c >> 1 of bytes 8 (c & 1) .. + 8
+                f16x8 o;
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    const uint32_t byte = (q[2 * (c & 1) + (e >> 2)] >> (8 * (e & 3))) & 0xFFu;
+                    o[e] = f16_of_f32(d * (float)((int)((c >> 1) ? (byte >> 4) : (byte & 0xFu)) - 8));
+                }
+                *reinterpret_cast<f16x8 *>(orow + (2 * g + h) * 32 + c * 8) = o;
+            }
+        }
     } else if constexpr (QT == NFAI_Q8_0_T16) {
         const u32x4 dv = load_nt16(t16_q80_d(W, nblk, tb) + r * 16);
 #pragma unroll
@@ -669,6 +712,8 @@ hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64
         k_dequant_t16<NFAI_Q6_K_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
     else if (type == NFAI_Q5_K_T16)
         k_dequant_t16<NFAI_Q5_K_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
+    else if (type == NFAI_Q4_0_T16)
+        k_dequant_t16<NFAI_Q4_0_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
     else if (type == NFAI_Q8_0_T16)
         k_dequant_t16<NFAI_Q8_0_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
     else return hipErrorInvalidValue;
@@ -819,6 +864,7 @@ hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s)
     if (a.w_type == NFAI_KQ_MIXED5) return q4t_bpw<NFAI_KQ_MIXED5, GEMV_QKV_ROPE>(p, bpw, grid, nw * 64, lds, s);
     if (a.w_type == NFAI_Q5_K_T16) return q4t_mode<NFAI_Q5_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     if (a.w_type == NFAI_Q8_0_T16) return q4t_mode<NFAI_Q8_0_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
+    if (a.w_type == NFAI_Q4_0_T16) return q4t_mode<NFAI_Q4_0_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     if (a.w_type == NFAI_Q4_K_T16) return q4t_mode<NFAI_Q4_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     return q4t_mode<NFAI_Q6_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
 }

@@ -43,6 +43,7 @@ struct Q4T { u32x4 q0, q1, hdr; };
 struct Q8T { u32x4 q[4]; u32x2 d; };
 struct Q5T { u32x4 q0, q1, hdr; u32x2 qh; };
 struct Q6T { u32x4 qla, qlb, qh, sc; uint32_t d; };
+struct Q40T { u32x4 q0, q1; uint32_t d; };
 
 __device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t mask, uint32_t bits) { return (a & mask) | bits; }
 
@@ -135,6 +136,47 @@ __device__ __forceinline__ float q4t_dot(const Q4T &w, const i32x4 (&af)[4], f32
     a = fmaf(-mv[0], sums[0], a);
     a = fmaf(scv[1], vhi, a);
     a = fmaf(-mv[1], sums[1], a);
+    return a;
+}
+
+// One step of a wave on a Q4_0 T16 tensor: the quants (2 x 1 KiB: q{h} = the 16 qs bytes of the lane's 32-block 2G + h) and the d of
+// the 16 rows (256 B); a lane of group G takes dword G of its row's d: d of 32-block 2G in the low half, of 2G + 1 in the high half
+// (9 VGPRs per step).
+__device__ __forceinline__ Q40T q40t_load_raw(const uint8_t *base, uint64_t n_tiles, uint32_t NB, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    const uint64_t tb = t16_tb(tile, NB, blk), nblk = t16_nblk(n_tiles, NB);
+    Q40T r;
+    r.q0 = load_nt16(t16_q40_qs(base, tb) + lane * 16);
+    r.q1 = load_nt16(t16_q40_qs(base, tb) + 1024 + lane * 16);
+    r.d = __builtin_nontemporal_load((const GLOBAL_AS uint32_t *)(t16_q40_d(base, nblk, tb) + (lane & 15) * 16 + (lane >> 4) * 4));
+    return r;
+}
+
+__device__ __forceinline__ Q40T q40t_load(const KqmParams &p, uint32_t seg, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    return q40t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
+}
+
+// 64 weights of one lane (32-blocks 2G: q0, 2G+1: q1) against the activations staged as for Q4_K.  The low nibbles of q{h} are weights
+// 0..15 of 32-block 2G + h (A-fragment slot 2h), the high nibbles weights 16..31 (slot 2h + 1): both halves of a 32-block accumulate
+// into ONE int32 accumulator, the block has one d.  The -8 of ggml's d * (q - 8) goes through the sum of x' over the block, as the mins
+// of Q4_K do: d * sum q x' - 8 d * sum x' (8 d is exact in fp32).  sums = {SX[2G], SX[2G+1]} of this super-block.
+__device__ __forceinline__ float q40t_dot(const Q40T &w, const i32x4 (&af)[4], f32x2 sums)
+{
+    constexpr uint32_t M = 0x0F0F0F0Fu;
+    i32x4 d0 = {0, 0, 0, 0}, d1 = {0, 0, 0, 0};
+    d0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[0], __builtin_bit_cast(i32x4, w.q0 & M), d0, 0, 0, 0);
+    d1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[2], __builtin_bit_cast(i32x4, w.q1 & M), d1, 0, 0, 0);
+    d0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[1], __builtin_bit_cast(i32x4, (w.q0 >> 4) & M), d0, 0, 0, 0);
+    d1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[3], __builtin_bit_cast(i32x4, (w.q1 >> 4) & M), d1, 0, 0, 0);
+    const float da = h2f_lo(w.d), db = h2f_hi(w.d);
+    // three signed base-256 digits of the fixed-point activations: sum q*x' = S0 + 256*S1 + 65536*S2 (integers, exact)
+    const float v0 = fmaf((float)d0[2], 65536.0f, fmaf((float)d0[1], 256.0f, (float)d0[0]));
+    const float v1 = fmaf((float)d1[2], 65536.0f, fmaf((float)d1[1], 256.0f, (float)d1[0]));
+    float a = da * v0;
+    a = fmaf(-(da * 8.0f), sums[0], a);
+    a = fmaf(db, v1, a);
+    a = fmaf(-(db * 8.0f), sums[1], a);
     return a;
 }
 
@@ -246,7 +288,7 @@ __device__ __forceinline__ float q6t_dot(const Q6T &w, const i32x4 (&af)[4], f32
 }
 
 // ---- a step against several activation vectors (the batched decode): unpack once, then one dot per column ------------------------------
-// The part of q4t_dot / q5t_dot / q6t_dot / q8t_dot that does not depend on x, done once per step: the four B operands (one byte per
+// The part of q4t_dot / q5t_dot / q6t_dot / q8t_dot / q40t_dot that does not depend on x, done once per step: the four B operands (one byte per
 // weight) and the scales.
 struct KqmW4 { i32x4 b[4]; float scv[2], mv[2]; };   // b[2n + hf]: low (n = 0) / high (n = 1) nibbles of q{hf}, the slot order of the A fragments
 struct KqmW6 { i32x4 b[4]; float sc[4]; float d; };  // b[qd], scales[8n + (G&1) + 2 qd] as floats
@@ -316,6 +358,23 @@ __device__ __forceinline__ KqmW4 kqm_unpack(const Q5T &w, uint32_t g)
         u.scv[h] = d * (float)sc;
         u.mv[h] = dmin * (float)mn;
     }
+    return u;
+}
+
+// Q4_0: the operand of Q4_K's columns.  b[] in the slot order of the Q4_K staging (slot 2h = low, 2h + 1 = high nibbles of q{h}), so
+// kqm_dot(KqmW4) sums slots 0, 1 (32-block 2G) and 2, 3 (32-block 2G+1); scale d, "min" 8 d: the arithmetic of q40t_dot.
+__device__ __forceinline__ KqmW4 kqm_unpack(const Q40T &w, uint32_t)
+{
+    constexpr uint32_t M = 0x0F0F0F0Fu;
+    KqmW4 u;
+    u.b[0] = __builtin_bit_cast(i32x4, w.q0 & M);
+    u.b[1] = __builtin_bit_cast(i32x4, (w.q0 >> 4) & M);
+    u.b[2] = __builtin_bit_cast(i32x4, w.q1 & M);
+    u.b[3] = __builtin_bit_cast(i32x4, (w.q1 >> 4) & M);
+    u.scv[0] = h2f_lo(w.d);
+    u.scv[1] = h2f_hi(w.d);
+    u.mv[0] = u.scv[0] * 8.0f;
+    u.mv[1] = u.scv[1] * 8.0f;
     return u;
 }
 

@@ -1,10 +1,10 @@
-// t16.h — the "T16" layout of ggml Q4_K / Q5_K / Q6_K / Q8_0 tensors in HBM: what it is, where every plane's bytes are, and how a
+// t16.h — the "T16" layout of ggml Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 tensors in HBM: what it is, where every plane's bytes are, and how a
 // block decodes.  The ONE definition: the repack kernels write it, the int8-MFMA GEMVs (kqm.h), the fp16 widening, the dequant-in-LDS
 // GEMM and the embedding gather read it, all through the helpers below.  Part of common.h (included there, behind the vector types
 // and load helpers it uses): include common.h, never this file alone.
 //
 // Repacked once at upload, same bytes as the native blocks.  Rows are grouped in tiles of 16; a "super-block" is 256 weights of one
-// row (one K-quant block, eight Q8_0 blocks), NB of them per row.  The native block is split into planes, one per field; inside a
+// row (one K-quant block, eight Q8_0 or Q4_0 blocks), NB of them per row.  The native block is split into planes, one per field; inside a
 // plane the records of (tile, blk) follow each other in the order tb = tile * NB + blk, 16 rows per record:
 //   Q4_K: plane 0  [tile][blk][h:2][lane:64][16 B]  lane = G*16 + r holds qs[32G+16h .. +16) of row 16*tile+r,
 //                  i.e. lane group G owns sub-blocks 2G (low nibbles) and 2G+1 (high nibbles) of its row;
@@ -22,6 +22,12 @@
 //                  row 16*tile+r: 16 weights of ONE 32-block (2h + (G >> 1)), so one d per lane and MFMA;
 //         plane 1  [tile][blk][r:16][16 B]          the eight fp16 d of that row and super-block, d of 32-block b at half
 //                                                   (b & 1) * 4 + (b >> 1): lanes of group G read the 8 bytes of their four d.
+//   Q4_0: plane 0  [tile][blk][h:2][lane:64][16 B]  lane = G*16 + r holds the 16 qs bytes of native 32-block 2G + h of super-block blk of
+//                  row 16*tile+r: its low nibbles are weights 32(2G+h) .. +16, its high nibbles weights 32(2G+h) + 16 .. +16, the
+//                  k ranges of A-fragment slots 2h and 2h + 1 of the Q4_K staging (kqm_stage<HAS4>), so lane group G owns
+//                  32-blocks 2G and 2G+1 as it owns sub-blocks 2G and 2G+1 of a Q4_K block: Q4_K's register shape per step;
+//         plane 1  [tile][blk][r:16][16 B]          the eight fp16 d of that row and super-block in block order: lanes of group G read
+//                                                   dword G, the d of their 32-blocks 2G (low half) and 2G+1 (high half).
 // Every wave-wide load is one contiguous kilobyte (quants), 512 bytes (Q5_K high bits) or 256 bytes (headers).
 // (The planar Q6_K layout of kernels_gemv_kq.hip, for row counts that are not a multiple of 16, is another format.)
 #pragma once
@@ -29,10 +35,12 @@
 namespace nfai {
 
 // Bytes per row and super-block of every plane: the native ggml block, split up.
-constexpr uint32_t GGML_Q4_K_BLOCK = 144, GGML_Q5_K_BLOCK = 176, GGML_Q6_K_BLOCK = 210, GGML_Q8_0_BLOCK = 34;
+constexpr uint32_t GGML_Q4_K_BLOCK = 144, GGML_Q5_K_BLOCK = 176, GGML_Q6_K_BLOCK = 210, GGML_Q8_0_BLOCK = 34, GGML_Q4_0_BLOCK = 18;
 constexpr uint32_t T16_K4_QS = 128, T16_K4_HDR = 16, T16_Q5K_QH = 32;  // Q4_K / Q5_K: qs | d, dmin, scales[12] | qh
 constexpr uint32_t T16_Q6K_Q = 192, T16_Q6K_SC = 16, T16_Q6K_D = 2;    // Q6_K: ql[128] + qh[64] | scales[16] | d
 constexpr uint32_t T16_Q80_QS = 256, T16_Q80_D = 16;                   // Q8_0: 8 x qs[32] | 8 x d
+constexpr uint32_t T16_Q40_QS = 128, T16_Q40_D = 16;                   // Q4_0: 8 x qs[16] | 8 x d
+static_assert(T16_Q40_QS + T16_Q40_D == 8 * GGML_Q4_0_BLOCK, "the T16 planes are the bytes of the native blocks (weight_row_bytes)");
 static_assert(T16_K4_QS + T16_K4_HDR == GGML_Q4_K_BLOCK && T16_K4_QS + T16_K4_HDR + T16_Q5K_QH == GGML_Q5_K_BLOCK &&
                   T16_Q6K_Q + T16_Q6K_SC + T16_Q6K_D == GGML_Q6_K_BLOCK && T16_Q80_QS + T16_Q80_D == 8 * GGML_Q8_0_BLOCK,
               "the T16 planes are the bytes of the native blocks (weight_row_bytes)");
@@ -51,6 +59,8 @@ T16_ADDR t16_q6k_sc(P base, uint64_t nblk, uint64_t tb) { return base + nblk * T
 T16_ADDR t16_q6k_d(P base, uint64_t nblk, uint64_t tb) { return base + nblk * (T16_Q6K_Q + T16_Q6K_SC) + tb * (16 * T16_Q6K_D); }  // + r * 2
 T16_ADDR t16_q80_qs(P base, uint64_t tb) { return base + tb * (16 * T16_Q80_QS); }                                                 // + h * 1024 + lane * 16
 T16_ADDR t16_q80_d(P base, uint64_t nblk, uint64_t tb) { return base + nblk * T16_Q80_QS + tb * (16 * T16_Q80_D); }                // + r * 16
+T16_ADDR t16_q40_qs(P base, uint64_t tb) { return base + tb * (16 * T16_Q40_QS); }                                                 // + h * 1024 + lane * 16
+T16_ADDR t16_q40_d(P base, uint64_t nblk, uint64_t tb) { return base + nblk * T16_Q40_QS + tb * (16 * T16_Q40_D); }                // + r * 16
 #undef T16_ADDR
 
 // ---- block decode ------------------------------------------------------------------------------------------------------------------
@@ -81,7 +91,7 @@ __device__ __forceinline__ int q6k_scale(const u32x4 sc, uint32_t si)
 }
 
 // Four consecutive elements k .. k+3 (k % 4 == 0) of row `row` of a T16 tensor with E columns and n_rows rows, as fp32: the block
-// exactly as ggml dequantises it (d * sc * q - dmin * m; d * sc * (q - 32); d * q), products and the difference rounded as written.
+// exactly as ggml dequantises it (d * sc * q - dmin * m; d * sc * (q - 32); d * q; d * (q - 8)), products and the difference rounded as written.
 __device__ __forceinline__ f32x4 t16_row_load4(const uint8_t *table, int type, uint64_t n_rows, uint64_t row, uint32_t k, uint32_t E)
 {
     typedef __attribute__((address_space(1))) uint8_t g8;
@@ -96,6 +106,15 @@ __device__ __forceinline__ f32x4 t16_row_load4(const uint8_t *table, int type, u
         const float d = (float)reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(t16_q80_d(t, nblk, tb) + r * 16)[(b32 & 1) * 4 + (b32 >> 1)];
 #pragma unroll
         for (int e = 0; e < 4; e++) out[e] = d * (float)(int8_t)((q4 >> (8 * e)) & 0xFFu);
+    } else if (type == NFAI_Q4_0_T16) {
+        const uint32_t b32 = kk >> 5, l = kk & 31;  // 32-block b32: lane group b32 >> 1, half b32 & 1; weight l: nibble l >> 4 of qs[l & 15]
+        const uint32_t q4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t16_q40_qs(t, tb) + (b32 & 1) * 1024 + ((b32 >> 1) * 16 + r) * 16 + (l & 15));
+        const float d = (float)reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(t16_q40_d(t, nblk, tb) + r * 16)[b32];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const uint32_t q = (q4 >> (8 * e)) & 0xFFu;
+            out[e] = d * (float)((int)((l >> 4) ? (q >> 4) : (q & 0xFu)) - 8);
+        }
     } else if (type == NFAI_Q4_K_T16 || type == NFAI_Q5_K_T16) {
         const uint32_t sb = kk >> 5, l = kk & 31;
         const g8 *hdr = t16_k4_hdr(t, nblk, tb) + r * 16;

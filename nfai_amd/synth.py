@@ -100,6 +100,47 @@ def quantize_q8_0(W) -> bytes:
     return out.tobytes()
 
 
+def quantize_q4_0(W) -> bytes:
+    """ggml quantize_row_q4_0_ref on every row of W [rows][cols] (cols % 32 == 0), restated from the format: per 32-block, max = the
+    element of largest magnitude WITH its sign (the first one among equals), d = max / -8, id = 1 / d (0 when d is 0),
+    q = min(15, int(x * id + 8.5)) (truncation; the argument is never negative), d stored as fp16; blocks of 18 bytes (fp16 d,
+    qs[16]: qs[j] = q[j] | q[j + 16] << 4), row-major.  Weight j decodes as d * (q[j] - 8): the extreme lands on code 0."""
+    x = np.asarray(W, dtype=np.float32).reshape(-1, 32)
+    idx = np.argmax(np.abs(x), axis=1)
+    mx = x[np.arange(x.shape[0]), idx]
+    d = (mx / np.float32(-8)).astype(np.float32)
+    inv = np.where(d != 0, np.float32(1) / np.where(d != 0, d, np.float32(1)), np.float32(0)).astype(np.float32)
+    q = np.minimum(15, (x * inv[:, None] + np.float32(8.5)).astype(np.int32)).astype(np.uint8)
+    out = np.empty((x.shape[0], 18), np.uint8)
+    out[:, :2] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
+    out[:, 2:] = q[:, :16] | (q[:, 16:] << 4)
+    return out.tobytes()
+
+
+def dequantize_q4_0(raw, rows: int, cols: int) -> np.ndarray:
+    """ggml dequantize_row_q4_0 on native blocks: float32 [rows][cols], weight j = d * ((qs[j] & 0xF) - 8), weight j + 16 =
+    d * ((qs[j] >> 4) - 8), the product rounded to fp32."""
+    b = np.frombuffer(bytes(raw), np.uint8).reshape(-1, 18)
+    d = b[:, :2].copy().view(np.float16).astype(np.float32)                      # [nb][1]
+    qs = b[:, 2:]
+    q = np.concatenate([qs & 0xF, qs >> 4], axis=1).astype(np.int32) - 8         # [nb][32]
+    return (d * q.astype(np.float32)).astype(np.float32).reshape(rows, cols)
+
+
+def q4_0_type(name: str, dims, mix: str = "q4_0") -> int:
+    """ggml type of a matrix in a Q4_0 file: Q4_0 (2) for every matrix, except Q6_K (14) for the lm_head (output.weight, or a tied
+    token_embd); an untied token_embd is Q4_0.  This is llama.cpp's rule for the file type as recalled: its source was not at hand
+    when this was written, so check it against a real file before relying on the head's type.  mix="all_q4_0": every matrix Q4_0,
+    the head and the embedding table too (so that the Q4_0 lm_head + ArgMax and embedding gather run)."""
+    if mix == "all_q4_0":
+        return 2
+    if mix != "q4_0":
+        raise ValueError(f"unknown Q4_0 mix {mix!r} (q4_0, all_q4_0)")
+    if name == "output.weight" or (name == "token_embd.weight" and dims.tied):
+        return 14
+    return 2
+
+
 def _f16_up(v):
     """The smallest fp16 values >= v (v >= 0, float32 array): a scale that a 6-bit code times it must still reach v."""
     h = np.asarray(v, np.float32).astype(np.float16)
