@@ -259,7 +259,14 @@ typedef struct nfai_llama_desc {
 } nfai_llama_desc;
 
 /* H/Hkv must be 1, 2, 3, 4 or 8 (NFAI_ERR_UNSUPPORTED otherwise) unless NFAI_LLAMA_UNFUSED, which takes any H/Hkv <= 8;
- * D 64 or 128; C <= 32768. */
+ * D 64 or 128; C <= 32768.
+ * RoPE and eps (NFAI_ERR_INVALID otherwise): rope_dims even and <= D; rope_n_freqs <= rope_dims / 2.  Pairs (2i, 2i + 1) with
+ * 2i < rope_dims are rotated by pos * rope_base^(-i / (rope_dims / 2)), by angle 0 where i >= rope_n_freqs; the elements at and
+ * past rope_dims are left as they are.  rope_dims = 0 means no rotation at all: every kernel then only reads (and ignores)
+ * in-bounds entries of tables that are sized by D.  eps is added to the mean square in every RMSNorm (each block's two and the
+ * output norm), on every path.  The members of a batch must agree in all four values (NFAI_ERR_UNSUPPORTED from _batch_create*).
+ * Tested on every path (tests/test_gpu_desc_forms.py): rope_dims in {0, 6, 24, D / 2, D}, rope_n_freqs full, 5 of 12 and 32 of
+ * 64, rope_base 1000, 10000 and 500000, eps 1e-5 and 1e-3. */
 int32_t nfai_hip_llama_create(nfai_ctx_t ctx, const nfai_llama_desc *desc, nfai_model_t *out);
 int32_t nfai_hip_llama_destroy(nfai_model_t model);
 /* GGUF tensor by name ("token_embd.weight", "blk.3.attn_q.weight", ..., "output_norm.weight",
