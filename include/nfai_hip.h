@@ -282,8 +282,37 @@ int32_t nfai_hip_llama_finalize(nfai_model_t model);
 /* Make `model` use the device-resident tensors `donor` already holds (same layer range, no copy, no second K-quant
  * repack): the in-flight sequences (slots) of a pipeline stage are separate models — own KV cache and position — over ONE set
  * of weights.  The reference aliases buffers the same way with ShaderProperty.BindShaderProprty (ShaderProperty.cs:95-108,
- * no reference count): `donor` must outlive `model`.  Call before nfai_hip_llama_finalize(model). */
+ * no reference count): `donor` must outlive `model`.  Call before nfai_hip_llama_finalize(model).
+ * Replacing a tensor of `donor` afterwards (_set_tensor + _finalize on the donor) INVALIDATES every model that shares it: the donor
+ * frees the storage the sharers still point to, and nothing tells them.  Replace tensors only on a model nobody shares, or destroy
+ * the sharers first and share again afterwards.  (A model that replaces its own tensor drops its graphs, engine plans and fp16
+ * prefill copies and rebuilds them on the next call; batches and windows over it answer NFAI_ERR_INVALID, "tensors changed", until
+ * they are created anew: tests/test_gpu_handoffs.py.) */
 int32_t nfai_hip_llama_share_tensors(nfai_model_t model, nfai_model_t donor);
+/* ---- what an advancing entry point leaves behind.  A sequence is the model's KV cache, position word, token word, token ring and
+ *      hidden-state pointer (_read which = 0).  Every entry point below may follow every other (tests/test_gpu_handoffs.py runs each
+ *      ordered pair); n is the number of tokens it ran, "last" the last of them.
+ *
+ *      entry point                               position   token word          ring              _read(0)
+ *      _decode_step, _decode_topk                + 1        ArgMax of the token  + that ArgMax     the token's hidden state
+ *      _decode_enqueue, _decode_greedy           + n        last ArgMax          + n ArgMaxes      last token's
+ *      _profile_step                             + 1        ArgMax               + 1               the token's
+ *      _profile_kernel                           + 1        ArgMax               + 1               unspecified (the replay overwrites
+ *                                                                                                  the activation vectors; _read(4),
+ *                                                                                                  the logits, are the token's)
+ *      _prefill, MFMA path (max_batch > 0)       + n        last token's ArgMax  not written       last token's
+ *      _ingest, MFMA path                        + n        unchanged            not written       last token's
+ *      _prefill / _ingest, token by token        as n _decode_step calls
+ *      _batch_step, _batch_step_topk (member i)  + 1        member i's ArgMax    + 1               member i's own vector
+ *      _batch_greedy (member i)                  + n        last ArgMax          + n               last token's
+ *      _window_step (t columns)                  + t        last column's ArgMax + t               last column's (held by the window)
+ *      _window_verify                            + acc + 1  a_acc                + acc + 1         last emitted column's
+ *      _set_pos, _reset                          = pos      unchanged            unchanged         unchanged
+ *
+ *      "not written": _fetch_tokens over positions the MFMA prefill ran returns whatever the ring held there.  _decode_enqueue
+ *      and _stage_step(NFAI_TOKEN_ON_DEVICE) continue from the token word, so behind an MFMA _ingest they feed the ArgMax of the last
+ *      token that formed logits; call _set_token first.  K / V rows at or above the position (rejected drafts, a rewound sequence,
+ *      the row _profile_kernel's replay writes) are never read and are overwritten by the next token. ---- */
 /* One token through embed -> blocks -> output_norm -> lm_head (LlamaModel.cs:116-125) at the
  * current position; logits_host (V floats) and argmax may be NULL.  Blocking. */
 int32_t nfai_hip_llama_decode_step(nfai_model_t model, uint32_t token, float *logits_host, uint32_t *argmax);
@@ -360,8 +389,13 @@ int32_t nfai_hip_llama_bytes_per_token(nfai_model_t model, uint32_t pos, uint64_
  * bench.py's roofline object).  ids: 0 qkv, 1 attn, 2 wo, 3 gateup, 4 down, 5 lmhead, 6 other. */
 int32_t nfai_hip_llama_profile_step(nfai_model_t model, uint32_t token, float *ms_by_class /* 8 */, uint32_t *launches_by_class /* 8 */);
 /* Average duration (us) of ONE kernel class: all its launches of a decode step (one per block, each on its own weights)
- * are replayed back to back, `reps` rounds, between a single pair of hipEvents on the launch stream (decode launches are
- * idempotent).  This is the per-launch duration rocprofv3 --kernel-trace reports; bench.py's roofline uses it. */
+ * are replayed back to back, `reps` rounds, between a single pair of hipEvents on the launch stream.  This is the per-launch
+ * duration rocprofv3 --kernel-trace reports; bench.py's roofline uses it.
+ * The token runs at position pos like _profile_step; the replay then runs with the position word already at pos + 1: a replayed
+ * q|k|v stores its K / V rows at pos + 1, a replayed attention reads rows 0 .. pos + 1.  Capacity rule: pos + 2 <= desc.C, else
+ * NFAI_ERR_KV_FULL before anything runs (position, logits and every cache row untouched).  A token >= n_vocab is NFAI_ERR_INVALID.
+ * Afterwards position, token word, ring, logits and every K / V row up to pos are what _decode_step leaves; the row at pos + 1 and
+ * the activation vectors (_read 0 .. 3) are unspecified. */
 int32_t nfai_hip_llama_profile_kernel(nfai_model_t model, uint32_t token, int32_t kernel_class, uint32_t reps, float *us_avg);
 
 /* ---- batched decode: n sequences advance one token each in ONE pass over the weights.  The reference serves one sequence per

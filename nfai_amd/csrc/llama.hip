@@ -354,6 +354,15 @@ int block_unfused(Model *m, Layer &L, LaunchTimer *timer)
     return NFAI_OK;
 }
 
+// Where one token of this model leaves its hidden state: the engine's blocks alternate between m->x and m->h, every other path ends in
+// m->x.  A replayed graph does not pass through enqueue_token, so every entry point that runs a token sets m->x_last from here: a
+// window or a batch may have pointed it into its own workspace since the graph was captured.
+const float *x_after_token(const Model *m)
+{
+    if (engine_ok(m) && m->eng_plans.size() == m->layers.size()) return ((m->layers.size() - 1) & 1) ? m->x : m->h;
+    return m->x;
+}
+
 }  // namespace
 
 namespace nfai {
@@ -410,7 +419,7 @@ int enqueue_token(Model *m, bool with_head, LaunchTimer *timer)
         return NFAI_OK;
     }
     Sched sch{m, timer};
-    const float *x_final = m->x;
+    const float *x_final = x_after_token(m);
     if (engine_ok(m) && m->eng_plans.size() == m->layers.size()) {
         // [q|k|v of the first block] then per block [attention] [engine: Wo -> gate|up -> Wdown -> next block's q|k|v].
         // The block input / output alternate between m->x and m->h so that no CU overwrites a vector another CU still reads.
@@ -421,7 +430,6 @@ int enqueue_token(Model *m, bool with_head, LaunchTimer *timer)
             S_TRY(submit_attn(m, L, sch));
             const EnginePlan plan = m->eng_plans[i];
             S_TRY(sch.submit(op_fn(KC_ENGINE, [plan](hipStream_t st) { return launch_engine(plan, st); })));
-            x_final = xout;
         }
     } else {
         for (Layer &L : m->layers) {
@@ -472,6 +480,7 @@ int run_token(Model *m, LaunchTimer *timer = nullptr)
     if (m->use_graph && !m->unfused && !timer) {
         S_TRY(ensure_graph(m));
         HIP_TRY(hipGraphLaunch(m->graph.exec, m->ctx->stream));
+        m->x_last = x_after_token(m);
     } else {
         S_TRY(enqueue_token(m, true, timer));
     }
@@ -882,6 +891,7 @@ static int step_blocking(Model *m, uint32_t token, bool topk = false, float temp
             if ((rc = ensure_sync_graph(m, sg, topk, temperature, k))) return rc;
             m->h_pin[2] = token;
             HIP_TRY(hipGraphLaunch(sg.graph.exec, s));
+            m->x_last = x_after_token(m);
             m->pos_host++;
         } else {
             if ((rc = set_token_async(m, token))) return rc;
@@ -1037,6 +1047,7 @@ NFAI_API int32_t nfai_hip_llama_stage_step(nfai_model_t h, uint32_t token, const
             m->stage_out = hidden_out;
         }
         HIP_TRY(hipGraphLaunch(m->stage_graph.exec, s));
+        m->x_last = x_after_token(m);
     } else {
         int rc = stage_enqueue(m, hidden_in, hidden_out);
         if (rc) return rc;
@@ -1157,6 +1168,12 @@ NFAI_API int32_t nfai_hip_llama_profile_kernel(nfai_model_t h, uint32_t token, i
     if (!us_avg || reps == 0 || cls < 0 || cls >= KC_N) return fail(NFAI_ERR_INVALID, "profile_kernel: bad arguments");
     if (!(m->first_stage && m->last_stage)) return fail(NFAI_ERR_STATE, "profile_kernel: whole-model contexts only");
     if (m->unfused) return fail(NFAI_ERR_STATE, "profile_kernel: fused path only");
+    if (token >= m->d.V) return fail(NFAI_ERR_INVALID, "profile_kernel: token %u >= vocab %u", token, m->d.V);
+    // The replayed launches read the position word AFTER the token advanced it: a replayed q|k|v stores its K / V rows at pos + 1 and
+    // a replayed attention reads rows 0 .. pos + 1.  Row pos + 1 must exist: refused before anything runs, like every capacity error.
+    if ((uint64_t)m->pos_host + 2 > m->d.C)
+        return fail(NFAI_ERR_KV_FULL, "profile_kernel: the token at position %u and the replay behind it need positions up to %u; the KV "
+                                      "capacity is %u", m->pos_host, m->pos_host + 1, m->d.C);
     int rc = set_token_async(m, token);
     if (rc) return rc;
     for (hipEvent_t &e : m->prof_rep_ev)
@@ -1169,8 +1186,11 @@ NFAI_API int32_t nfai_hip_llama_profile_kernel(nfai_model_t h, uint32_t token, i
     if (rc) return rc;
     if (m->prof_ops.empty()) return fail(NFAI_ERR_STATE, "profile_kernel: no launch of class %d in a step", cls);
     // Replay: every launch of the class in a step (one per block: 28 different weight sets at 3B, far beyond the 256 MB
-    // Infinity Cache, so nothing is re-read from cache), `reps` rounds, back to back between ONE pair of events.  Decode
-    // launches are idempotent (outputs never alias inputs), so the replay leaves the model state as the step left it.
+    // Infinity Cache, so nothing is re-read from cache), `reps` rounds, back to back between ONE pair of events.  The replay runs at
+    // the ADVANCED position word: it leaves the position, the token word, the ring, the logits and every K / V row at or below the
+    // token's own as the step left them; it overwrites the K / V rows at position + 1 (which the next token writes before anyone
+    // reads them) and the activation vectors (a replayed first q|k|v launch also redoes the token prologue: the embedding row of
+    // the ArgMax lands in the hidden-state vector).
     hipStream_t s = m->ctx->stream;
     // Engine launches hand vectors over under a per-token tag: a replay with the tag unchanged would find every hand-off already
     // complete and never wait.  So each replayed engine launch is preceded by the one-block kernel that advances the tag (as in
