@@ -255,6 +255,38 @@ NFAI_API uint32_t nfai_hip_debug_gemm_last(uint32_t *desc16, uint32_t max_desc)
     return desc16 ? gemm_last(reinterpret_cast<GemmDesc *>(desc16), max_desc) : 0;
 }
 
+// Which fp16 / fp32 GEMV forms ran: one descriptor of 16 words per launch_gemv call that stayed on the fp16 / fp32 path since the
+// last call, on any context, oldest first — kernel (0 = k_gemv, 1 = k_gemv_sk), weight type, mode, norm, begin, xd, UPW | CH, U | RW,
+// guard, threads per workgroup, grid, dynamic LDS bytes, NU, K, fused ArgMax, prefetch-only (GemvDesc).  Returns the number written
+// (at most max_desc, the newest ones).  Host side only: a replayed graph records nothing.
+NFAI_API uint32_t nfai_hip_debug_gemv_last(uint32_t *desc16, uint32_t max_desc)
+{
+    static_assert(sizeof(GemvDesc) == 16 * sizeof(uint32_t), "sixteen words per launch");
+    return desc16 ? gemv_last(reinterpret_cast<GemvDesc *>(desc16), max_desc) : 0;
+}
+
+// The descriptor launch_gemv would launch with for these arguments (rows0..2: GemvArgs::seg_rows; q|k|v: q, k, v rows, gate|up: F, F),
+// without a device: the planner launch_gemv itself calls, n_cu from the argument.  0, or NFAI_ERR_INVALID where launch_gemv refuses.
+NFAI_API int32_t nfai_hip_debug_gemv_plan(int32_t w_type, int32_t mode, uint32_t rows0, uint32_t rows1, uint32_t rows2, uint32_t K, uint32_t n_cu,
+                                          int32_t norm, int32_t fused_argmax, uint32_t *desc16)
+{
+    static float some_float;        // non-null stand-ins: the planner asks only whether these are set
+    static uint32_t some_word;
+    if (!desc16 || mode < GEMV_PLAIN || mode > GEMV_GATEUP || n_cu == 0) return NFAI_ERR_INVALID;
+    GemvArgs a;
+    a.w_type = w_type;
+    a.mode = mode;
+    a.seg_rows[0] = rows0; a.seg_rows[1] = rows1; a.seg_rows[2] = rows2;
+    a.K = K;
+    a.n_cu = n_cu;
+    if (norm) a.gamma = &some_float;
+    if (fused_argmax) { a.argmax_part = &some_float; a.argmax_out = &some_word; }
+    GemvDesc d;
+    if (gemv_plan(a, d) != hipSuccess) return NFAI_ERR_INVALID;
+    memcpy(desc16, &d, sizeof d);
+    return NFAI_OK;
+}
+
 static int canary_check_all(Ctx *c);  // NFAI_HIP_DEBUG_CANARY (below, with nfai_hip_buf_alloc)
 
 NFAI_API int32_t nfai_hip_ctx_synchronize(nfai_ctx_t h)

@@ -158,6 +158,23 @@ inline int ggml_type_of(int t)
 }
 
 hipError_t launch_gemv(const GemvArgs &a, hipStream_t s);     // any weight type; K-quants go to launch_gemv_kq / _kqm
+// How one fp16 / fp32 GEMV is launched, sixteen words: what gemv_plan decides, what launch_gemv launches from, and what the test
+// hooks nfai_hip_debug_gemv_plan / nfai_hip_debug_gemv_last report.
+struct GemvDesc {
+    uint32_t kernel;             // 0: k_gemv (persistent), 1: k_gemv_sk (split-K)
+    uint32_t w_type, mode, norm;
+    uint32_t begin;              // first launch of a token (GemvArgs::Begin)
+    uint32_t xd;                 // rows dealt to the XCDs by share
+    uint32_t upw_ch, u_rw;       // k_gemv: UPW, U; k_gemv_sk: CH, RW
+    uint32_t guard;
+    uint32_t threads, grid, lds_bytes;   // threads per workgroup, workgroups, dynamic LDS bytes of the launch
+    uint32_t NU, K;
+    uint32_t argmax;             // fused ArgMax
+    uint32_t prefetch_only;
+};
+constexpr uint32_t GEMV_RING_N = 256;
+hipError_t gemv_plan(const GemvArgs &a, GemvDesc &d);  // host arithmetic only (no HIP call); d.NU == 0 with hipSuccess: nothing to launch
+uint32_t gemv_last(GemvDesc *out, uint32_t max_desc);  // the launch_gemv calls of the fp16 / fp32 path since the last call, oldest first (the newest GEMV_RING_N at most)
 bool gemv_begin_ok(const GemvArgs &a);                         // can this q|k|v launch carry the per-token prologue (GemvArgs::Begin)?
 // Measures how fast the workgroups of each blockIdx % 8 label (= one XCD each) stream from HBM with every CU streaming, and derives
 // the dealing shares of GemvArgs::xcd_shares; nullptr when switched off (NFAI_XCD_DEAL=0) or when the probe could not run.

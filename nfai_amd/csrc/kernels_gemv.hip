@@ -634,30 +634,30 @@ static SkPlan plan_gemv_sk(const GemvArgs &a, uint32_t NU, int epl, int rpu)
 }
 
 template <int WT, int MODE, int CH, int RW>
-static hipError_t launch_sk(const GemvParams &p, const SkPlan &sp, hipStream_t s)
+static hipError_t launch_sk(const GemvParams &p, const GemvDesc &d, hipStream_t s)
 {
-    if (p.gamma != nullptr) hipLaunchKernelGGL((k_gemv_sk<WT, MODE, CH, RW, true>), dim3(sp.grid), dim3(sp.nw * 64), 0, s, p);
-    else hipLaunchKernelGGL((k_gemv_sk<WT, MODE, CH, RW, false>), dim3(sp.grid), dim3(sp.nw * 64), 0, s, p);
+    if (d.norm) hipLaunchKernelGGL((k_gemv_sk<WT, MODE, CH, RW, true>), dim3(d.grid), dim3(d.threads), d.lds_bytes, s, p);
+    else hipLaunchKernelGGL((k_gemv_sk<WT, MODE, CH, RW, false>), dim3(d.grid), dim3(d.threads), d.lds_bytes, s, p);
     return hipGetLastError();
 }
 
 template <int WT, int MODE>
-static hipError_t dispatch_sk(const GemvParams &p, const SkPlan &sp, hipStream_t s)
+static hipError_t dispatch_sk(const GemvParams &p, const GemvDesc &d, hipStream_t s)
 {
-#define NFAI_SK(CH_, RW_) if (sp.ch == CH_ && sp.rw == RW_) return launch_sk<WT, MODE, CH_, RW_>(p, sp, s);
+#define NFAI_SK(CH_, RW_) if (d.upw_ch == CH_ && d.u_rw == RW_) return launch_sk<WT, MODE, CH_, RW_>(p, d, s);
     NFAI_SK(1, 4) NFAI_SK(1, 8) NFAI_SK(1, 16) NFAI_SK(2, 4) NFAI_SK(2, 8) NFAI_SK(4, 4)
 #undef NFAI_SK
     return hipErrorInvalidValue;
 }
 
 template <int WT>
-static hipError_t dispatch_sk_mode(const GemvParams &p, const SkPlan &sp, int mode, hipStream_t s)
+static hipError_t dispatch_sk_mode(const GemvParams &p, const GemvDesc &d, hipStream_t s)
 {
-    switch (mode) {
-        case GEMV_PLAIN: return dispatch_sk<WT, GEMV_PLAIN>(p, sp, s);
-        case GEMV_RESIDUAL: return dispatch_sk<WT, GEMV_RESIDUAL>(p, sp, s);
-        case GEMV_QKV_ROPE: return dispatch_sk<WT, GEMV_QKV_ROPE>(p, sp, s);
-        case GEMV_GATEUP: return dispatch_sk<WT, GEMV_GATEUP>(p, sp, s);
+    switch (d.mode) {
+        case GEMV_PLAIN: return dispatch_sk<WT, GEMV_PLAIN>(p, d, s);
+        case GEMV_RESIDUAL: return dispatch_sk<WT, GEMV_RESIDUAL>(p, d, s);
+        case GEMV_QKV_ROPE: return dispatch_sk<WT, GEMV_QKV_ROPE>(p, d, s);
+        case GEMV_GATEUP: return dispatch_sk<WT, GEMV_GATEUP>(p, d, s);
     }
     return hipErrorInvalidValue;
 }
@@ -728,44 +728,44 @@ static std::atomic<uint64_t> g_dealt{0};   // launches of the XD instantiations 
 uint64_t gemv_dealt_launches() { return g_dealt.load(); }
 
 template <int WT, int MODE, int UPW, int U, bool GUARD>
-static hipError_t launch_one(const GemvParams &p, const GemvPlan &pl, hipStream_t s)
+static hipError_t launch_one(const GemvParams &p, const GemvDesc &d, hipStream_t s)
 {
     if constexpr (MODE == GEMV_QKV_ROPE) {
-        if (p.gamma != nullptr && p.begin.on) {  // the token's first launch: its own instantiation, nothing of it in the other 27
-            hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, true, true>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, s, p);
+        if (d.norm && d.begin) {  // the token's first launch: its own instantiation, nothing of it in the other 27
+            hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, true, true>), dim3(d.grid), dim3(d.threads), d.lds_bytes, s, p);
             return hipGetLastError();
         }
     }
     if constexpr (!GUARD && WT == NFAI_F16 && (MODE == GEMV_PLAIN || MODE == GEMV_GATEUP)) {
-        if (p.xd.S != 0) {  // rows dealt to the XCDs by calibrated share (the lm_head, gate | up): own instantiations
-            if (p.gamma != nullptr)
-                hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, true, false, true>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, s, p);
+        if (d.xd) {  // rows dealt to the XCDs by calibrated share (the lm_head, gate | up): own instantiations
+            if (d.norm)
+                hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, true, false, true>), dim3(d.grid), dim3(d.threads), d.lds_bytes, s, p);
             else
-                hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, false, false, true>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, s, p);
+                hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, false, false, true>), dim3(d.grid), dim3(d.threads), d.lds_bytes, s, p);
             g_dealt++;
             return hipGetLastError();
         }
     }
-    if (p.gamma != nullptr)
-        hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, true>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, s, p);
+    if (d.norm)
+        hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, true>), dim3(d.grid), dim3(d.threads), d.lds_bytes, s, p);
     else
-        hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, false>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, s, p);
+        hipLaunchKernelGGL((k_gemv<WT, MODE, UPW, U, GUARD, false>), dim3(d.grid), dim3(d.threads), d.lds_bytes, s, p);
     return hipGetLastError();
 }
 
 template <int WT, int MODE>
-static hipError_t dispatch_plan(const GemvParams &p, const GemvPlan &pl, hipStream_t s)
+static hipError_t dispatch_plan(const GemvParams &p, const GemvDesc &d, hipStream_t s)
 {
-    if (pl.guard) {
-        switch (pl.upw) {
-            case 1: return launch_one<WT, MODE, 1, 1, true>(p, pl, s);
-            case 2: return launch_one<WT, MODE, 2, 1, true>(p, pl, s);
-            case 3: return launch_one<WT, MODE, 3, 1, true>(p, pl, s);
-            default: return launch_one<WT, MODE, 4, 1, true>(p, pl, s);
+    if (d.guard) {
+        switch (d.upw_ch) {
+            case 1: return launch_one<WT, MODE, 1, 1, true>(p, d, s);
+            case 2: return launch_one<WT, MODE, 2, 1, true>(p, d, s);
+            case 3: return launch_one<WT, MODE, 3, 1, true>(p, d, s);
+            default: return launch_one<WT, MODE, 4, 1, true>(p, d, s);
         }
     }
 #define NFAI_CASE(UPW_, U_) \
-    if (pl.upw == UPW_ && pl.u == U_) return launch_one<WT, MODE, UPW_, U_, false>(p, pl, s);
+    if (d.upw_ch == UPW_ && d.u_rw == U_) return launch_one<WT, MODE, UPW_, U_, false>(p, d, s);
     NFAI_CASE(1, 1) NFAI_CASE(1, 2) NFAI_CASE(1, 3) NFAI_CASE(1, 4)
     NFAI_CASE(2, 1) NFAI_CASE(2, 2) NFAI_CASE(2, 3) NFAI_CASE(2, 4)
     NFAI_CASE(3, 1) NFAI_CASE(3, 2) NFAI_CASE(3, 3) NFAI_CASE(3, 4)
@@ -775,26 +775,119 @@ static hipError_t dispatch_plan(const GemvParams &p, const GemvPlan &pl, hipStre
 }
 
 template <int WT>
-static hipError_t dispatch_mode(const GemvParams &p, const GemvPlan &pl, int mode, hipStream_t s)
+static hipError_t dispatch_mode(const GemvParams &p, const GemvDesc &d, hipStream_t s)
 {
-    switch (mode) {
-        case GEMV_PLAIN: return dispatch_plan<WT, GEMV_PLAIN>(p, pl, s);
-        case GEMV_RESIDUAL: return dispatch_plan<WT, GEMV_RESIDUAL>(p, pl, s);
-        case GEMV_QKV_ROPE: return dispatch_plan<WT, GEMV_QKV_ROPE>(p, pl, s);
-        case GEMV_GATEUP: return dispatch_plan<WT, GEMV_GATEUP>(p, pl, s);
+    switch (d.mode) {
+        case GEMV_PLAIN: return dispatch_plan<WT, GEMV_PLAIN>(p, d, s);
+        case GEMV_RESIDUAL: return dispatch_plan<WT, GEMV_RESIDUAL>(p, d, s);
+        case GEMV_QKV_ROPE: return dispatch_plan<WT, GEMV_QKV_ROPE>(p, d, s);
+        case GEMV_GATEUP: return dispatch_plan<WT, GEMV_GATEUP>(p, d, s);
     }
     return hipErrorInvalidValue;
+}
+
+// The one place that decides how an fp16 / fp32 GEMV is launched: every check of launch_gemv that depends on the shape, the two
+// shape pickers, and the gate of the XD dealing, written into the descriptor launch_gemv then launches from (and
+// nfai_hip_debug_gemv_plan reports).  Host arithmetic only: reads the scalar fields of `a`, whether its pointers are null, and the
+// eight xcd_shares; d.NU == 0 with hipSuccess: nothing to launch.
+hipError_t gemv_plan(const GemvArgs &a, GemvDesc &d)
+{
+    d = GemvDesc{};
+    const int rpu = (a.mode == GEMV_QKV_ROPE || a.mode == GEMV_GATEUP) ? 2 : 1;
+    const int epl = a.w_type == NFAI_F16 ? 8 : 4;
+    if (a.w_type != NFAI_F16 && a.w_type != NFAI_F32) return hipErrorInvalidValue;
+    if (a.K == 0 || a.K % 8 != 0) return hipErrorInvalidValue;
+    const uint32_t total_rows = a.seg_rows[0] + a.seg_rows[1] + a.seg_rows[2];
+    uint32_t NU;
+    if (a.mode == GEMV_QKV_ROPE) {
+        // rotation pairs must not straddle a segment or a head
+        if ((a.seg_rows[0] | a.seg_rows[1] | a.seg_rows[2] | a.D) & 1u) return hipErrorInvalidValue;
+        NU = total_rows / 2;
+    } else if (a.mode == GEMV_GATEUP) {
+        if (a.seg_rows[0] != a.seg_rows[1]) return hipErrorInvalidValue;
+        NU = a.seg_rows[0];
+    } else {
+        NU = a.seg_rows[0];
+    }
+    if (NU == 0) return hipSuccess;
+    if (a.begin.on) {
+        if (a.mode != GEMV_QKV_ROPE || !a.gamma || !a.begin.freqs || !a.begin.cs_out || (a.begin.emb && (!a.begin.tok || !a.begin.x_out)) ||
+            a.begin.n_freq * 2 > BEGIN_CS_WORDS)
+            return hipErrorInvalidValue;  // (gemv_begin_ok() says which launches take it)
+    }
+    if (a.argmax_part && (a.mode != GEMV_PLAIN || !a.argmax_out)) return hipErrorInvalidValue;
+    d.w_type = (uint32_t)a.w_type;
+    d.mode = (uint32_t)a.mode;
+    d.norm = a.gamma != nullptr;
+    d.begin = a.begin.on;
+    d.K = a.K;
+    d.argmax = a.argmax_part != nullptr;
+    d.prefetch_only = a.prefetch_only;
+    const SkPlan sp = plan_gemv_sk(a, NU, epl, rpu);
+    if (sp.ok) {
+        d.kernel = 1;
+        d.upw_ch = (uint32_t)sp.ch;
+        d.u_rw = (uint32_t)sp.rw;
+        d.threads = sp.nw * 64;
+        d.grid = sp.grid;
+        d.NU = NU;
+        return hipSuccess;
+    }
+    const GemvPlan pl = plan_gemv(NU, a.K, epl, rpu, a.n_cu, a.gamma != nullptr, a.mode);
+    if (!pl.ok || (a.argmax_part && pl.grid > ARGMAX_FUSED_MAX_BLOCKS)) return hipErrorInvalidValue;
+    if (pl.lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    if (a.xcd_shares && !pl.guard && !a.prefetch_only && a.w_type == NFAI_F16 && (a.mode == GEMV_PLAIN || a.mode == GEMV_GATEUP) && pl.grid % 8 == 0 &&
+        (NU + pl.upw - 1) / pl.upw >= 8u * pl.grid * (pl.block / 64)) {   // >= 8 groups per wave: a share moves a fraction of a wave's work (at
+                                                                          // gate | up's 4 groups per wave a share is a whole group: measured slower)
+        bool uniform = true, sane = true;
+        for (int x = 0; x < 8; x++) {
+            uniform = uniform && a.xcd_shares[x] == a.xcd_shares[0];
+            sane = sane && a.xcd_shares[x] >= 1 && a.xcd_shares[x] <= 1024;
+        }
+        if (sane && !uniform) d.xd = 1;   // equal shares: the plain dealing is the same partition, one instantiation fewer in flight
+    }
+    d.upw_ch = (uint32_t)pl.upw;
+    d.u_rw = (uint32_t)pl.u;
+    d.guard = pl.guard;
+    d.threads = pl.block;
+    d.grid = pl.grid;
+    d.lds_bytes = pl.lds_bytes;
+    d.NU = NU;
+    return hipSuccess;
+}
+
+// Test hook (nfai_hip_debug_gemv_last): the descriptor of every launch_gemv call on the fp16 / fp32 path, in a ring of host words —
+// tests prove through it which kernel form their shape reached.  Sixteen words per launch (GemvDesc); built as gemm_note / gemm_last.
+static GemvDesc g_gemv_ring[GEMV_RING_N];
+static std::atomic<uint32_t> g_gemv_head{0}, g_gemv_tail{0};  // launches noted / launches already read
+
+static void gemv_note(const GemvDesc &d)
+{
+    const uint32_t i = g_gemv_head.fetch_add(1, std::memory_order_relaxed);
+    g_gemv_ring[i % GEMV_RING_N] = d;
+}
+
+uint32_t gemv_last(GemvDesc *out, uint32_t max_desc)
+{
+    const uint32_t head = g_gemv_head.load(std::memory_order_relaxed);
+    uint32_t tail = g_gemv_tail.exchange(head, std::memory_order_relaxed);
+    if (head - tail > GEMV_RING_N) tail = head - GEMV_RING_N;   // the ring holds the newest GEMV_RING_N
+    if (head - tail > max_desc) tail = head - max_desc;
+    for (uint32_t i = tail; i != head; i++) out[i - tail] = g_gemv_ring[i % GEMV_RING_N];
+    return head - tail;
 }
 
 hipError_t launch_gemv(const GemvArgs &a, hipStream_t s)
 {
     if (is_t16(a.w_type) || a.w_type == NFAI_KQ_MIXED || a.w_type == NFAI_KQ_MIXED5) return launch_gemv_kqm(a, s);
     if (a.w_type == NFAI_Q4_K || a.w_type == NFAI_Q6_K) return launch_gemv_kq(a, s);
+    GemvDesc d;
+    {
+        const hipError_t e = gemv_plan(a, d);
+        if (e != hipSuccess || d.NU == 0) return e;
+    }
     GemvParams p{};
-    const int rpu = (a.mode == GEMV_QKV_ROPE || a.mode == GEMV_GATEUP) ? 2 : 1;
     const int epl = a.w_type == NFAI_F16 ? 8 : 4;
-    if (a.w_type != NFAI_F16 && a.w_type != NFAI_F32) return hipErrorInvalidValue;
-    if (a.K == 0 || a.K % 8 != 0) return hipErrorInvalidValue;
     uint32_t total_rows = 0;
     for (int i = 0; i < 3; i++) {
         p.W[i] = reinterpret_cast<const uint8_t *>(a.W[i]);
@@ -803,17 +896,7 @@ hipError_t launch_gemv(const GemvArgs &a, hipStream_t s)
     p.seg_end[0] = a.seg_rows[0];
     p.seg_end[1] = a.seg_rows[0] + a.seg_rows[1];
     p.seg_end[2] = total_rows;
-    if (a.mode == GEMV_QKV_ROPE) {
-        // rotation pairs must not straddle a segment or a head
-        if ((a.seg_rows[0] | a.seg_rows[1] | a.seg_rows[2] | a.D) & 1u) return hipErrorInvalidValue;
-        p.NU = total_rows / 2;
-    } else if (a.mode == GEMV_GATEUP) {
-        if (a.seg_rows[0] != a.seg_rows[1]) return hipErrorInvalidValue;
-        p.NU = a.seg_rows[0];
-    } else {
-        p.NU = a.seg_rows[0];
-    }
-    if (p.NU == 0) return hipSuccess;
+    p.NU = d.NU;
     p.row_bytes = (uint64_t)a.K * (a.w_type == NFAI_F16 ? 2 : 4);
     p.x = a.x;
     p.gamma = a.gamma;
@@ -831,55 +914,42 @@ hipError_t launch_gemv(const GemvArgs &a, hipStream_t s)
     p.pos = a.pos_dev;
     p.kv_f16 = a.kv_type == NFAI_F16;
     p.prefetch_only = a.prefetch_only ? 1u : 0u;
-    const SkPlan sp = plan_gemv_sk(a, p.NU, epl, rpu);
     if (a.begin.on) {
-        if (a.mode != GEMV_QKV_ROPE || !a.gamma || !a.begin.freqs || !a.begin.cs_out || (a.begin.emb && (!a.begin.tok || !a.begin.x_out)) ||
-            a.begin.n_freq * 2 > BEGIN_CS_WORDS)
-            return hipErrorInvalidValue;  // (gemv_begin_ok() says which launches take it)
         p.begin.on = 1; p.begin.emb = static_cast<const uint8_t *>(a.begin.emb); p.begin.emb_type = a.begin.emb_type; p.begin.emb_rows = a.begin.emb_rows;
         p.begin.tok = a.begin.tok; p.begin.x_out = a.begin.x_out; p.begin.freqs = a.begin.freqs; p.begin.cs_out = a.begin.cs_out;
         p.begin.n_freq = a.begin.n_freq; p.begin.epoch = a.begin.epoch;
     }
     if (a.argmax_part) {
-        if (a.mode != GEMV_PLAIN || !a.argmax_out) return hipErrorInvalidValue;
         p.am.part_v = static_cast<float *>(a.argmax_part);
         p.am.part_i = reinterpret_cast<uint32_t *>(p.am.part_v + ARGMAX_FUSED_MAX_BLOCKS);
         p.am.ticket = p.am.part_i + ARGMAX_FUSED_MAX_BLOCKS;
         p.am.out_idx = a.argmax_out; p.am.pos_inc = a.argmax_pos_inc; p.am.ring = a.argmax_ring; p.am.ring_len = a.argmax_ring_len;
     }
-    if (sp.ok) {
+    gemv_note(d);
+    if (d.kernel == 1) {
         p.KC = a.K / (64 * epl);
-        if (a.argmax_part && sp.grid > ARGMAX_FUSED_MAX_BLOCKS) return hipErrorInvalidValue;
         static const char *sk_names[] = {"gemv_sk_plain", "gemv_sk_residual", "gemv_sk_qkv_rope", "gemv_sk_gateup"};
-        NFAI_STAMP_SET(p, sk_names[a.mode & 3], sp.grid, sp.nw * 64);
-        if (a.w_type == NFAI_F16) return dispatch_sk_mode<NFAI_F16>(p, sp, a.mode, s);
-        return dispatch_sk_mode<NFAI_F32>(p, sp, a.mode, s);
+        NFAI_STAMP_SET(p, sk_names[a.mode & 3], d.grid, d.threads);
+        if (a.w_type == NFAI_F16) return dispatch_sk_mode<NFAI_F16>(p, d, s);
+        return dispatch_sk_mode<NFAI_F32>(p, d, s);
     }
-    const GemvPlan pl = plan_gemv(p.NU, a.K, epl, rpu, a.n_cu, a.gamma != nullptr, a.mode);
-    if (!pl.ok || (a.argmax_part && pl.grid > ARGMAX_FUSED_MAX_BLOCKS)) return hipErrorInvalidValue;
     p.KC = (a.K + 64 * epl - 1) / (64 * epl);
-    if (pl.lds_bytes > 160 * 1024) return hipErrorInvalidValue;
     p.xd.S = 0;
-    if (a.xcd_shares && !pl.guard && !a.prefetch_only && a.w_type == NFAI_F16 && (a.mode == GEMV_PLAIN || a.mode == GEMV_GATEUP) && pl.grid % 8 == 0 &&
-        (p.NU + pl.upw - 1) / pl.upw >= 8u * pl.grid * (pl.block / 64)) {   // >= 8 groups per wave: a share moves a fraction of a wave's work (at
-                                                                           // gate | up's 4 groups per wave a share is a whole group: measured slower)
+    if (d.xd) {   // the gate is gemv_plan's
         uint32_t off = 0;
-        bool uniform = true, sane = true;
         for (int x = 0; x < 8; x++) {
             p.xd.n[x] = a.xcd_shares[x];
             p.xd.off[x] = (uint16_t)off;
             off += a.xcd_shares[x];
-            uniform = uniform && a.xcd_shares[x] == a.xcd_shares[0];
-            sane = sane && a.xcd_shares[x] >= 1 && a.xcd_shares[x] <= 1024;
         }
-        if (sane && !uniform) p.xd.S = off;   // equal shares: the plain dealing is the same partition, one instantiation fewer in flight
+        p.xd.S = off;
     }
     {
         static const char *names[] = {"gemv_plain", "gemv_residual", "gemv_qkv_rope", "gemv_gateup"};
-        NFAI_STAMP_SET(p, names[a.mode & 3], pl.grid, pl.block);
+        NFAI_STAMP_SET(p, names[a.mode & 3], d.grid, d.threads);
     }
-    if (a.w_type == NFAI_F16) return dispatch_mode<NFAI_F16>(p, pl, a.mode, s);
-    return dispatch_mode<NFAI_F32>(p, pl, a.mode, s);
+    if (a.w_type == NFAI_F16) return dispatch_mode<NFAI_F16>(p, d, s);
+    return dispatch_mode<NFAI_F32>(p, d, s);
 }
 
 // ---- per-XCD streaming shares ----------------------------------------------------------------------------------------------------
