@@ -153,6 +153,25 @@ public sealed unsafe class HipLlamaModel : IInferenceProvider
             Native.Check(Native.nfai_hip_llama_ingest(model, p, (uint)tokens.Length));
     }
 
+    /// <summary>Log-probabilities of every position (nfai_hip_llama_score): n passes of the loop LlamaModel.cs:116-125, each followed
+    /// by the log of SamplingUtils.Softmax (SamplingUtils.cs:35-41) at the row's target and SamplingUtils.ArgMax (:55-56).  The tokens
+    /// run at the current position and leave their K / V rows.  targets == null: row i scores tokens[i + 1], the last row nothing
+    /// (LogProb = 0).  On the MFMA prefill path when the model was created with MaxBatch > 0.</summary>
+    public (float[] LogProb, uint[] ArgMax, float[] LogProbMax) Score(uint[] tokens, uint[]? targets = null)
+    {
+        if (targets != null && targets.Length != tokens.Length) throw new ArgumentException("Score: one target per token", nameof(targets));
+        var logProb = new float[tokens.Length];
+        var argMax = new uint[tokens.Length];
+        var logProbMax = new float[tokens.Length];
+        fixed (uint* t = tokens)
+        fixed (uint* g = targets)                                                               // null array -> null pointer
+        fixed (float* lp = logProb)
+        fixed (uint* am = argMax)
+        fixed (float* lpm = logProbMax)
+            Native.Check(Native.nfai_hip_llama_score(model, t, (uint)tokens.Length, g, lp, am, lpm));
+        return (logProb, argMax, logProbMax);
+    }
+
     private readonly uint[] candidateIds = new uint[TopK];
     private readonly float[] candidateProbs = new float[TopK];
     private const int TopK = 40;                                                                // SamplingUtils.cs:5 defaults

@@ -167,6 +167,18 @@ int32_t nfai_hip_topk(nfai_ctx_t ctx, nfai_buf_t x, uint32_t n, float temperatur
  * buffer, a buffer shorter than n floats, rows * n beyond the context's top-k scratch.  Blocking. */
 int32_t nfai_hip_topk_rows(nfai_ctx_t ctx, const nfai_buf_t *x /* [rows] */, uint32_t rows, uint32_t n, float temperature, uint32_t k,
                            uint32_t *ids_out /* [rows][k] */, float *probs_out /* [rows][k] */);
+/* Log-probabilities of T rows of fp32 logits ([T][ld], row r at r * ld, V <= ld columns used): per row the log of
+ * SamplingUtils.Softmax (SamplingUtils.cs:35-41: exp(l - max) / sum) at targets[r] -> logprob[r], SamplingUtils.ArgMax
+ * (SamplingUtils.cs:55-56: the FIRST index of the maximum) -> argmax[r], and the log-probability of that maximum -> logprob_max[r].
+ * targets[r] == NFAI_SCORE_NO_TARGET: logprob[r] = 0.  The row is folded into a running state {max, sum exp(l - max), first index
+ * of the max, target logit} `slab` columns per pass (0 = all V in one pass; otherwise a multiple of 64, the last pass is shorter):
+ * an online softmax, the sum rescaled whenever the maximum moves.  Deterministic for a given slab width; columns at or past V are
+ * never read.  NFAI_ERR_INVALID: T or V = 0, ld < V, slab not 0 and not a multiple of 64, a buffer too small, a target >= V that is
+ * not NFAI_SCORE_NO_TARGET (found on the device: none of the three outputs is written by that call).  Blocking. */
+#define NFAI_SCORE_NO_TARGET 0xFFFFFFFFu
+int32_t nfai_hip_score_rows(nfai_ctx_t ctx, nfai_buf_t logits, uint32_t T, uint32_t V, uint32_t ld, uint32_t slab /* columns per pass, 0 = V */,
+                            nfai_buf_t targets /* [T] u32 */, nfai_buf_t logprob /* [T] f32 */, nfai_buf_t argmax /* [T] u32 */,
+                            nfai_buf_t logprob_max /* [T] f32 */);
 
 /* ---- fused operators (no reference counterpart: each replaces the chain named) ---- */
 /* scores -> softmax -> weighted sum in one KV-cache pass, GQA heads sharing each K/V read.
@@ -303,6 +315,8 @@ int32_t nfai_hip_llama_share_tensors(nfai_model_t model, nfai_model_t donor);
  *      _prefill, MFMA path (max_batch > 0)       + n        last token's ArgMax  not written       last token's
  *      _ingest, MFMA path                        + n        unchanged            not written       last token's
  *      _prefill / _ingest, token by token        as n _decode_step calls
+ *      _score, MFMA path                         + n        last token's ArgMax  not written       last token's (as _prefill)
+ *      _score, M = 1 path                        as n _decode_step calls
  *      _batch_step, _batch_step_topk (member i)  + 1        member i's ArgMax    + 1               member i's own vector
  *      _batch_greedy (member i)                  + n        last ArgMax          + n               last token's
  *      _window_step (t columns)                  + t        last column's ArgMax + t               last column's (held by the window)
@@ -346,6 +360,29 @@ int32_t nfai_hip_llama_prefill(nfai_model_t model, const uint32_t *tokens, uint3
  * M = 1 path token by token otherwise (bit-identical to _decode_step).  n == 0 is a no-op.  NFAI_ERR_KV_FULL when pos + n exceeds
  * the KV capacity, before anything runs.  Blocking. */
 int32_t nfai_hip_llama_ingest(nfai_model_t model, const uint32_t *tokens, uint32_t n);
+/* Score a token sequence: n passes of the loop LlamaModel.cs:116-125, each followed by SamplingUtils.Softmax on its logits
+ * (SamplingUtils.cs:35-41; the reference overwrites those logits, LlamaModel.cs:103-126) — here every position's are kept long
+ * enough to take, per row i: logprob[i] = log softmax(logits_i)[targets[i]], argmax[i] = SamplingUtils.ArgMax(logits_i)
+ * (SamplingUtils.cs:55-56) and logprob_max[i], its log-probability (nfai_hip_score_rows per row).  targets == NULL scores the
+ * sequence itself: row i takes tokens[i + 1], the last row no target (logprob[n - 1] = 0); a target NFAI_SCORE_NO_TARGET scores
+ * nothing on its row.  Any of the three outputs may be NULL.  Tokens run at positions pos..pos+n-1 and leave their K / V rows.
+ * MFMA path (the admission of _prefill, V %% 64 == 0 and an fp16 / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 head): chunks of max_batch
+ * rows through the blocks as _prefill, then per chunk the output norm of all rows and the head as fp16 GEMMs over slabs of 8192
+ * vocabulary columns (a quantised head is widened one slab at a time), each folded into the rows' running state: no [n][V] logits
+ * and no fp16 copy of the head exist.  The rows' logits come from fp16 operands (normalised row rounded to fp16 x fp16 head,
+ * fp32 accumulate): 2e-2 * max(1, max|logit|) per logit, twice that per log-probability.  The last token then runs the head exactly
+ * as _prefill does (fp32 GEMV + ArgMax), so the model is left bit for bit where nfai_hip_llama_prefill(tokens, n) leaves it.
+ * M = 1 path (anything else): per token the body of _decode_step, then the row kernels on its fp32 logits: the reference's
+ * arithmetic; the model is left as n _decode_step calls leave it.
+ * Workspace, allocated by the first call and freed with the model: the fp32 slab [max_batch rounded up to 128][min(V, 8192)], the
+ * fp16 scratch [min(V, 8192)][E] of a quantised head, 16 bytes of state per row and 16 bytes per KV position for targets and
+ * outputs — 16.8 + 50.3 MB at 3B with max_batch 512; the M = 1 path takes the per-position part only.
+ * Errors, before anything runs: NFAI_ERR_INVALID for NULL tokens, n = 0, a token >= V, a target >= V that is not
+ * NFAI_SCORE_NO_TARGET; NFAI_ERR_KV_FULL when pos + n exceeds the KV capacity; NFAI_ERR_UNSUPPORTED for a pipeline stage that is
+ * not the whole network.  Blocking. */
+int32_t nfai_hip_llama_score(nfai_model_t model, const uint32_t *tokens, uint32_t n,
+                             const uint32_t *targets /* [n] or NULL = tokens[i + 1], last row no target */,
+                             float *logprob /* [n] or NULL */, uint32_t *argmax /* [n] or NULL */, float *logprob_max /* [n] or NULL */);
 /* Pipeline stage: run this stage's blocks on a hidden state resident in device memory.
  * First stage: hidden_in == NULL and `token` is embedded.  Last stage: lm_head + argmax run and
  * `logits_host`/`argmax` are filled (blocking) when non-NULL.  Otherwise enqueue only. */

@@ -15,6 +15,7 @@ BATCH_QUANT = 1   # nfai_batch_flags: nfai_hip_llama_batch_create_ex admits Q4_K
 BATCH_QUANT_ANY = 4   # with BATCH_QUANT: Q5_K, Q8_0 and Q4_0 matrices too (bit 1 is reserved)
 LLAMA_UNFUSED, LLAMA_NO_GRAPH, LLAMA_KV_F16, LLAMA_PREFETCH, LLAMA_ENGINE = 1, 2, 4, 8, 16
 TOKEN_ON_DEVICE = 0xFFFFFFFF
+SCORE_NO_TARGET = 0xFFFFFFFF   # NFAI_SCORE_NO_TARGET: a row of nfai_hip_score_rows / nfai_hip_llama_score without a target
 
 
 class NfaiHipError(RuntimeError):
@@ -87,6 +88,7 @@ SIGNATURES = {
     "nfai_hip_argmax": [H, H, u32, H],
     "nfai_hip_topk": [H, H, u32, f32, u32, C.POINTER(u32), C.POINTER(f32)],
     "nfai_hip_topk_rows": [H, C.POINTER(H), u32, u32, f32, u32, C.POINTER(u32), C.POINTER(f32)],
+    "nfai_hip_score_rows": [H, H, u32, u32, u32, u32, H, H, H, H],
     "nfai_hip_attn_decode": [H, H, H, H, H, u32, u32, u32, u32, u32, i32],
     "nfai_hip_gemv_fused": [H, H, i32, H, H, f32, H, H, u32, u32],
     "nfai_hip_lmhead_argmax": [H, H, i32, H, H, f32, H, H, u32, u32],
@@ -107,6 +109,7 @@ SIGNATURES = {
     "nfai_hip_llama_fetch_tokens": [H, u32, C.POINTER(u32)],
     "nfai_hip_llama_prefill": [H, C.POINTER(u32), u32, C.POINTER(f32)],
     "nfai_hip_llama_ingest": [H, C.POINTER(u32), u32],
+    "nfai_hip_llama_score": [H, C.POINTER(u32), u32, C.POINTER(u32), C.POINTER(f32), C.POINTER(u32), C.POINTER(f32)],
     "nfai_hip_llama_stage_step": [H, u32, vp, vp, C.POINTER(f32), C.POINTER(u32)],
     "nfai_hip_llama_stage_ingest": [H, C.POINTER(u32), vp, vp, u32],
     "nfai_hip_llama_token_to_device": [H, vp],

@@ -21,7 +21,7 @@ OUT = os.path.join(CSRC, "libnfai_hip.so")
 OBJ_DIR = os.path.join(CSRC, "build")
 ARCH = "gfx950"
 
-SOURCES = ["api.hip", "kernels_basic.hip", "kernels_gemv.hip", "kernels_gemv_batch.hip", "kernels_gemv_batch_kqm.hip", "kernels_gemv_wide.hip", "kernels_gemv_kq.hip", "kernels_gemv_kqm.hip", "kernels_attn.hip", "kernels_attn_window.hip", "kernels_engine.hip", "kernels_prefill.hip", "llama.hip", "llama_prefill.hip", "llama_batch.hip", "pp.hip"]
+SOURCES = ["api.hip", "kernels_basic.hip", "kernels_gemv.hip", "kernels_gemv_batch.hip", "kernels_gemv_batch_kqm.hip", "kernels_gemv_wide.hip", "kernels_gemv_kq.hip", "kernels_gemv_kqm.hip", "kernels_attn.hip", "kernels_attn_window.hip", "kernels_engine.hip", "kernels_prefill.hip", "kernels_score.hip", "llama.hip", "llama_prefill.hip", "llama_batch.hip", "pp.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kqm.h"), os.path.join(CSRC, "t16.h"), os.path.join(CSRC, "llama.h"), os.path.join(ROOT, "include", "nfai_hip.h")]
 
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall",

@@ -842,6 +842,48 @@ NFAI_API int32_t nfai_hip_topk_rows(nfai_ctx_t h, const nfai_buf_t *x, uint32_t 
     return NFAI_OK;
 }
 
+// Log softmax (SamplingUtils.cs:35-41) at a target, ArgMax (SamplingUtils.cs:55-56) and its log-probability for T rows of logits,
+// `slab` columns per pass (kernels_score.hip).  The rows' running state and the error word live in a buffer of the call's own (16
+// bytes per row: T is not bounded by the context scratch); not a hot path — the model entry keeps its workspace.
+NFAI_API int32_t nfai_hip_score_rows(nfai_ctx_t h, nfai_buf_t logits, uint32_t T, uint32_t V, uint32_t ld, uint32_t slab, nfai_buf_t targets,
+                                     nfai_buf_t logprob, nfai_buf_t argmax, nfai_buf_t logprob_max)
+{
+    CTX_OR_FAIL(c, h);
+    BUF_OR_FAIL(bl, logits);
+    BUF_OR_FAIL(bt, targets);
+    BUF_OR_FAIL(bp, logprob);
+    BUF_OR_FAIL(ba, argmax);
+    BUF_OR_FAIL(bm, logprob_max);
+    if (T == 0 || V == 0) return fail(NFAI_ERR_INVALID, "score_rows: T=%u V=%u", T, V);
+    if (ld < V) return fail(NFAI_ERR_INVALID, "score_rows: ld=%u < V=%u", ld, V);
+    if (slab % 64) return fail(NFAI_ERR_INVALID, "score_rows: slab=%u is neither 0 nor a multiple of 64", slab);
+    NEED(bl, (uint64_t)(T - 1) * ld + V, 4);
+    NEED(bt, T, 4);
+    NEED(bp, T, 4);
+    NEED(ba, T, 4);
+    NEED(bm, T, 4);
+    const uint32_t ns_max = slab ? slab : V;
+    char *work = nullptr;
+    const size_t state_bytes = (size_t)T * sizeof(ScoreState);
+    if (hipMalloc(reinterpret_cast<void **>(&work), state_bytes + 16) != hipSuccess) return fail(NFAI_ERR_OOM, "score_rows: %zu bytes of row state", state_bytes + 16);
+    ScoreState *state = reinterpret_cast<ScoreState *>(work);
+    uint32_t *err = reinterpret_cast<uint32_t *>(work + state_bytes);
+    uint32_t bad = 0;
+    hipError_t e = hipMemsetAsync(err, 0, 4, c->stream);
+    for (uint32_t c0 = 0; c0 < V && e == hipSuccess; c0 += ns_max)
+        e = launch_score_slab(static_cast<const float *>(bl->ptr) + c0, T, ld, c0, std::min(ns_max, V - c0), V, static_cast<const uint32_t *>(bt->ptr), state,
+                              err, c->stream);
+    if (e == hipSuccess)
+        e = launch_score_finish(state, T, static_cast<const uint32_t *>(bt->ptr), err, static_cast<float *>(bp->ptr), static_cast<uint32_t *>(ba->ptr),
+                                static_cast<float *>(bm->ptr), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);   // also on an error path: the state is freed behind whatever was enqueued
+    hipFree(work);
+    if (e != hipSuccess || es != hipSuccess) return fail(NFAI_ERR_HIP, "score_rows: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    if (bad) return fail(NFAI_ERR_INVALID, "score_rows: a target is >= V=%u and not NFAI_SCORE_NO_TARGET (no output was written)", V);
+    return NFAI_OK;
+}
+
 // ---- fused operators -------------------------------------------------------------------------
 // Scalars the fused kernels read from device memory (so graphs can be replayed) live at the END
 // of the context scratch area when the op-level entry points are used.

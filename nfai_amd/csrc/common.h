@@ -190,6 +190,9 @@ hipError_t launch_repack_q40_t16(const void *native, void *tiled, uint64_t rows,
 hipError_t launch_embed_kqt(const void *table, int type, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E, hipStream_t s);
 hipError_t launch_embed_rows_kqt(const void *table, int type, uint64_t n_rows, const uint32_t *toks, float *y, uint32_t T, uint32_t E, hipStream_t s);
 hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64_t cols, void *out_f16, hipStream_t s);  // T16 K-quant / Q8_0 -> fp16 [rows][cols]
+// Tiles [tile0, tile0 + n_tiles) of the same tensor (rows 16 * tile0 ..) -> fp16 [16 * n_tiles][cols]: the planes are addressed
+// through the tensor's TOTAL row count (t16.h), so a row range cannot be widened by offsetting W.
+hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64_t cols, uint64_t tile0, uint64_t n_tiles, void *out_f16, hipStream_t s);
 // Q6_K super-blocks are 210 bytes (not 16-byte aligned): in HBM they live as four planes
 // ql | qh | scales | d (same bytes, naturally aligned accesses).  nblk = rows * cols / 256.
 hipError_t launch_repack_q6k(const void *native, void *planes, uint64_t nblk, hipStream_t s);
@@ -489,6 +492,22 @@ hipError_t launch_topk_rows(const TopkRowsArgs &rows, uint32_t R, uint32_t n, fl
 // launch + 8k + 8 bytes back + the host half (api.hip); blocking
 void topk_finish(const float *vals, const uint32_t *ids, float M, float S, float temperature, uint32_t k, uint32_t *ids_out, float *probs_out);
 int topk_run(Ctx *c, const float *logits_dev, uint32_t n, float temperature, uint32_t k, void *work, uint32_t *ids_out, float *probs_out);
+// ---- log-probabilities of logit rows (kernels_score.hip) ----------------------------------------------------------------------------
+// The running state of one row across column slabs: an online softmax (SamplingUtils.cs:35-41) + ArgMax (:55-56) + the target's logit.
+struct ScoreState {
+    float m;        // max of the columns folded so far
+    float s;        // sum exp(l - m) over them
+    uint32_t idx;   // first index of m
+    float tl;       // logit of the row's target, once its column has passed
+};
+constexpr uint32_t SCORE_NO_TARGET = 0xFFFFFFFFu;
+// Folds columns [c0, c0 + ns) of T rows into state[T]: row r's columns are slab[r * ld + 0 .. ns) (`slab` points AT column c0).
+// c0 == 0 starts a row's state.  targets[r] >= V and not SCORE_NO_TARGET: *err |= 1 (checked in the c0 == 0 pass).  One workgroup per row.
+hipError_t launch_score_slab(const float *slab, uint32_t T, uint64_t ld, uint32_t c0, uint32_t ns, uint32_t V, const uint32_t *targets,
+                             ScoreState *state, uint32_t *err, hipStream_t s);
+// logprob[r] = tl - m - log s (0 without a target), argmax[r] = idx, logprob_max[r] = -log s; writes nothing when *err != 0
+hipError_t launch_score_finish(const ScoreState *state, uint32_t T, const uint32_t *targets, const uint32_t *err, float *logprob, uint32_t *argmax,
+                               float *logprob_max, hipStream_t s);
 // per-token prologue: embed row -> x, cos/sin table for the current position
 hipError_t launch_token_begin(const void *table, int type, const uint32_t *tok, float *x, uint32_t E,
                               const float *freqs, float *rope_cs, uint32_t n_freq, const uint32_t *pos_dev,

@@ -595,14 +595,16 @@ __device__ __forceinline__ _Float16 f16_of_f32(float v)
     return (_Float16)v;
 }
 template <int QT>
-__global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 *out, uint32_t n_tiles, uint32_t NB)
+__global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 *out, uint32_t n_tiles, uint32_t NB, uint32_t tile0, uint32_t all_tiles)
 {
     __shared__ __attribute__((aligned(16))) uint8_t stage[4][16 * DQ_ROW];
-    const uint64_t tb = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tb >= (uint64_t)n_tiles * NB) return;
+    // the launch covers tiles [tile0, tile0 + n_tiles) of a tensor of all_tiles tiles: `tile` counts output rows, `tb` the tensor's records
+    const uint64_t tb_out = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tb_out >= (uint64_t)n_tiles * NB) return;
     const uint32_t lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
-    const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB);
-    const uint64_t nblk = t16_nblk(n_tiles, NB);
+    const uint32_t tile = (uint32_t)(tb_out / NB), blk = (uint32_t)(tb_out % NB);
+    const uint64_t tb = tb_out + (uint64_t)tile0 * NB;
+    const uint64_t nblk = t16_nblk(all_tiles, NB);
     _Float16 *orow = reinterpret_cast<_Float16 *>(stage[threadIdx.x >> 6] + r * DQ_ROW);
     if constexpr (QT == NFAI_Q4_K_T16 || QT == NFAI_Q5_K_T16) {
         const u32x4 q0 = load_nt16(t16_k4_qs(W, tb) + lane * 16), q1 = load_nt16(t16_k4_qs(W, tb) + 1024 + lane * 16);
@@ -700,24 +702,26 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
     }
 }
 
+hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64_t cols, uint64_t tile0, uint64_t n_tiles, void *out_f16, hipStream_t s)
+{
+    if (n_tiles == 0) return hipSuccess;
+    if (rows % 16 || cols % 256 || tile0 + n_tiles > rows / 16) return hipErrorInvalidValue;
+    const uint64_t all = rows / 16, nb = cols / 256, grid = (n_tiles * nb + 3) / 4;
+    if (grid > 0x7FFFFFFFull || all > 0xFFFFFFFFull) return hipErrorInvalidValue;
+#define NFAI_DQ(QT) k_dequant_t16<QT><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb, (uint32_t)tile0, (uint32_t)all)
+    if (type == NFAI_Q4_K_T16) NFAI_DQ(NFAI_Q4_K_T16);
+    else if (type == NFAI_Q6_K_T16) NFAI_DQ(NFAI_Q6_K_T16);
+    else if (type == NFAI_Q5_K_T16) NFAI_DQ(NFAI_Q5_K_T16);
+    else if (type == NFAI_Q4_0_T16) NFAI_DQ(NFAI_Q4_0_T16);
+    else if (type == NFAI_Q8_0_T16) NFAI_DQ(NFAI_Q8_0_T16);
+    else return hipErrorInvalidValue;
+#undef NFAI_DQ
+    return hipGetLastError();
+}
+
 hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64_t cols, void *out_f16, hipStream_t s)
 {
-    if (rows == 0) return hipSuccess;
-    if (rows % 16 || cols % 256) return hipErrorInvalidValue;
-    const uint64_t n_tiles = rows / 16, nb = cols / 256, grid = (n_tiles * nb + 3) / 4;
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (type == NFAI_Q4_K_T16)
-        k_dequant_t16<NFAI_Q4_K_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
-    else if (type == NFAI_Q6_K_T16)
-        k_dequant_t16<NFAI_Q6_K_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
-    else if (type == NFAI_Q5_K_T16)
-        k_dequant_t16<NFAI_Q5_K_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
-    else if (type == NFAI_Q4_0_T16)
-        k_dequant_t16<NFAI_Q4_0_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
-    else if (type == NFAI_Q8_0_T16)
-        k_dequant_t16<NFAI_Q8_0_T16><<<(uint32_t)grid, 256, 0, s>>>(static_cast<const uint8_t *>(W), static_cast<_Float16 *>(out_f16), (uint32_t)n_tiles, (uint32_t)nb);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return launch_dequant_t16_f16(W, type, rows, cols, 0, rows / 16, out_f16, s);
 }
 
 // ---- dispatch ------------------------------------------------------------------------------------------

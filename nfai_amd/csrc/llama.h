@@ -157,6 +157,10 @@ struct Model {
     void *d_argmax_part = nullptr;
     void *d_topk = nullptr;          // workspace of the top-k candidate launch (allocated by the first nfai_hip_llama_decode_topk)
     float *d_attn_part = nullptr;
+    // workspace of nfai_hip_llama_score (allocated by its first call): per KV position targets | logprob | argmax | logprob_max, then
+    // one ScoreState per chunk row and the error word; MFMA path: the fp32 logit slab [pf.T][min(V, 8192)] and, for a quantised head,
+    // the fp16 scratch [min(V, 8192)][E] one slab of it is widened into
+    void *d_score = nullptr, *d_score_slab = nullptr, *d_score_wide = nullptr;
     // activations
     float *x = nullptr, *h = nullptr, *q = nullptr, *att = nullptr, *act = nullptr, *logits = nullptr;
     // extra activations of the unfused 1:1 chain
@@ -237,5 +241,6 @@ int set_token_async(Model *m, uint32_t tok);
 int engine_failed(Model *m, uint32_t code);
 int enqueue_token(Model *m, bool with_head, LaunchTimer *timer = nullptr);
 int stage_enqueue(Model *m, const void *hidden_in, void *hidden_out);
+int step_token_blocking(Model *m, uint32_t token);   // the body of nfai_hip_llama_decode_step: one token, blocking, nothing downloaded
 
 }  // namespace nfai

@@ -673,7 +673,7 @@ NFAI_API int32_t nfai_hip_llama_destroy(nfai_model_t h)
         free_t(L.ffn_norm); free_t(L.wgate); free_t(L.wup); free_t(L.wdown);
         hipFree(L.kcache); hipFree(L.vcache);
     }
-    void *ptrs[] = {m->d_topk, m->d_engparams, m->d_gran, m->d_epoch, m->d_pos, m->d_tok, m->d_ring, m->d_freqs, m->d_ropecs, m->d_argmax_part, m->d_attn_part, m->x, m->h,
+    void *ptrs[] = {m->d_score, m->d_score_slab, m->d_score_wide, m->d_topk, m->d_engparams, m->d_gran, m->d_epoch, m->d_pos, m->d_tok, m->d_ring, m->d_freqs, m->d_ropecs, m->d_argmax_part, m->d_attn_part, m->x, m->h,
                     m->q, m->att, m->act, m->logits, m->xn, m->qraw, m->scores, m->wts, m->proj, m->gate, m->up};
     for (void *p : ptrs) if (p) hipFree(p);
     void *pfp[] = {m->pf.CS, m->pf.toks, m->pf.X, m->pf.H1, m->pf.Q, m->pf.K, m->pf.V, m->pf.ATT, m->pf.G, m->pf.U, m->pf.SC,
@@ -918,6 +918,10 @@ static int step_blocking(Model *m, uint32_t token, bool topk = false, float temp
         m->pos_host = pos;
     }
 }
+
+namespace nfai {
+int step_token_blocking(Model *m, uint32_t token) { return step_blocking(m, token); }
+}  // namespace nfai
 
 NFAI_API int32_t nfai_hip_llama_decode_step(nfai_model_t h, uint32_t token, float *logits_host, uint32_t *argmax)
 {

@@ -328,6 +328,26 @@ static int ensure_wide_shadow(Model *m)
     return NFAI_OK;
 }
 
+// Logits of the LAST prompt token: output norm + lm_head + argmax on its hidden state (m->x).  The position was already advanced
+// past the prompt, so the head runs without the token bookkeeping.
+static int prefill_head(Model *m)
+{
+    hipStream_t s = m->ctx->stream;
+    LaunchTimer *timer = nullptr;
+    const Tensor &head = m->output.ptr ? m->output : m->token_embd;
+    GemvArgs a = gemv_base(m, head, m->x, m->d.E);
+    a.gamma = static_cast<const float *>(m->output_norm.ptr);
+    a.y = m->logits;
+    const bool am_fused = head.type == NFAI_F16 || head.type == NFAI_F32 || is_t16(head.type);
+    if (am_fused) {  // ArgMax in the lm_head launch, as in a decode step; no bookkeeping: the position was set by the last chunk
+        a.argmax_part = static_cast<char *>(m->d_argmax_part) + 4096;
+        a.argmax_out = m->d_tok;
+    }
+    K_TRY(KC_LMHEAD, launch_gemv(a, s));
+    if (!am_fused) K_TRY(KC_OTHER, launch_argmax(m->logits, m->d.V, m->d_tok, m->d_argmax_part, nullptr, nullptr, 0, s));
+    return NFAI_OK;
+}
+
 // head = false: only the KV cache is filled (nfai_hip_llama_ingest: prompt tokens whose output the reference's loop discards).
 static int prefill_impl(nfai_model_t h, const uint32_t *tokens, uint32_t n, float *logits_last_host, bool head)
 {
@@ -354,22 +374,7 @@ static int prefill_impl(nfai_model_t h, const uint32_t *tokens, uint32_t n, floa
         if (rc) return rc;
         done += T;
     }
-    // logits of the LAST prompt token: output norm + lm_head + argmax on its hidden state.  The
-    // position was already advanced past the prompt, so the head runs without the token bookkeeping.
-    if (head) {
-        LaunchTimer *timer = nullptr;
-        const Tensor &head = m->output.ptr ? m->output : m->token_embd;
-        GemvArgs a = gemv_base(m, head, m->x, m->d.E);
-        a.gamma = static_cast<const float *>(m->output_norm.ptr);
-        a.y = m->logits;
-        const bool am_fused = head.type == NFAI_F16 || head.type == NFAI_F32 || is_t16(head.type);
-        if (am_fused) {  // ArgMax in the lm_head launch, as in a decode step; no bookkeeping: the position was set above
-            a.argmax_part = static_cast<char *>(m->d_argmax_part) + 4096;
-            a.argmax_out = m->d_tok;
-        }
-        K_TRY(KC_LMHEAD, launch_gemv(a, s));
-        if (!am_fused) K_TRY(KC_OTHER, launch_argmax(m->logits, m->d.V, m->d_tok, m->d_argmax_part, nullptr, nullptr, 0, s));
-    }
+    if (head) S_TRY(prefill_head(m));
     if (head && logits_last_host) HIP_TRY(hipMemcpyAsync(logits_last_host, m->logits, (size_t)m->d.V * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));  // `tokens` is the caller's (pageable) memory: the copy into the workspace has left it by now
     return NFAI_OK;
@@ -390,6 +395,118 @@ NFAI_API int32_t nfai_hip_llama_ingest(nfai_model_t h, const uint32_t *tokens, u
         return NFAI_OK;
     }
     return prefill_impl(h, tokens, n, nullptr, false);
+}
+
+// ---- nfai_hip_llama_score: the log-probabilities of every position (include/nfai_hip.h) ---------------------------------------------
+// Vocabulary columns per pass of the head on the MFMA path: the fp32 slab [pf.T][SCORE_NS] is 16.8 MB at max_batch 512, the fp16
+// scratch of a quantised head [SCORE_NS][E] 50.3 MB at E = 3072.
+constexpr uint32_t SCORE_NS = 8192;
+
+static bool score_mfma_ok(const Model *m)
+{
+    if (!prefill_mfma_ok(m) || m->d.V % 64) return false;
+    const Tensor &head = m->output.ptr ? m->output : m->token_embd;
+    return head.type == NFAI_F16 || is_t16(head.type);
+}
+
+// The head over the T hidden rows a prefill_chunk left in w.X: output norm of every row, then per slab of the vocabulary the fp16
+// GEMM into the slab buffer and the row kernel that folds it into the rows' state; the finish kernel writes rows [at, at + T) of the
+// device output arrays.
+static int score_chunk_head(Model *m, uint32_t T, const uint32_t *d_tgt, ScoreState *state, uint32_t *d_err, float *d_lp, uint32_t *d_am, float *d_lpm)
+{
+    const nfai_llama_desc &d = m->d;
+    Model::Prefill &w = m->pf;
+    hipStream_t s = m->ctx->stream;
+    const Tensor &head = m->output.ptr ? m->output : m->token_embd;
+    const uint32_t NS = std::min(d.V, SCORE_NS);
+    float *slab = static_cast<float *>(m->d_score_slab);
+#define SC_TRY(expr)                                                                                             \
+    do {                                                                                                         \
+        hipError_t _e = (expr);                                                                                  \
+        if (_e != hipSuccess)                                                                                    \
+            return fail(_e == hipErrorInvalidValue ? NFAI_ERR_INVALID : NFAI_ERR_HIP, "score: %s failed: %s", #expr, \
+                        hipGetErrorString(_e));                                                                  \
+    } while (0)
+    SC_TRY(launch_rmsnorm_rows(w.X, static_cast<const float *>(m->output_norm.ptr), w.XN, T, d.E, d.eps, s));
+    for (uint32_t c0 = 0; c0 < d.V; c0 += NS) {
+        const uint32_t ns = std::min(NS, d.V - c0);   // V % 64 == 0: the last slab is a multiple of 64 too
+        GemmArgs g;
+        g.A = w.XN; g.lda = d.E; g.ldb = d.E; g.M = T; g.N = ns; g.K = d.E;
+        g.C = slab; g.ldc = NS;
+        g.n_cu = (uint32_t)m->ctx->prop.multiProcessorCount;
+        if (head.type == NFAI_F16) {
+            g.B = static_cast<const uint8_t *>(head.ptr) + (uint64_t)c0 * d.E * 2;
+        } else {   // rows c0 .. c0 + ns of the quantised head, widened (64 | c0, ns: whole tiles of 16 rows)
+            SC_TRY(launch_dequant_t16_f16(head.ptr, head.type, head.rows, head.cols, c0 / 16, ns / 16, m->d_score_wide, s));
+            g.B = m->d_score_wide;
+        }
+        SC_TRY(launch_gemm_f16(g, s));
+        SC_TRY(launch_score_slab(slab, T, NS, c0, ns, d.V, d_tgt, state, d_err, s));
+    }
+    SC_TRY(launch_score_finish(state, T, d_tgt, d_err, d_lp, d_am, d_lpm, s));
+#undef SC_TRY
+    return NFAI_OK;
+}
+
+NFAI_API int32_t nfai_hip_llama_score(nfai_model_t h, const uint32_t *tokens, uint32_t n, const uint32_t *targets, float *logprob, uint32_t *argmax,
+                                      float *logprob_max)
+{
+    MODEL_OR_FAIL(m, h);
+    NEED_FINAL(m);
+    const nfai_llama_desc &d = m->d;
+    if (!(m->first_stage && m->last_stage)) return fail(NFAI_ERR_UNSUPPORTED, "score: the model is a pipeline stage, not the whole network");
+    if (!tokens || n == 0) return fail(NFAI_ERR_INVALID, "score: empty sequence");
+    for (uint32_t i = 0; i < n; i++)
+        if (tokens[i] >= d.V) return fail(NFAI_ERR_INVALID, "score: token %u >= vocab %u", tokens[i], d.V);
+    if (targets)
+        for (uint32_t i = 0; i < n; i++)
+            if (targets[i] >= d.V && targets[i] != NFAI_SCORE_NO_TARGET) return fail(NFAI_ERR_INVALID, "score: target %u (row %u) >= vocab %u", targets[i], i, d.V);
+    if ((uint64_t)m->pos_host + n > d.C) return fail(NFAI_ERR_KV_FULL, "score: %u tokens from position %u exceed KV capacity %u", n, m->pos_host, d.C);
+    const bool mfma = score_mfma_ok(m);
+    hipStream_t s = m->ctx->stream;
+    // the workspace (sizes: include/nfai_hip.h).  n <= C, a chunk has at most max(1, max_batch) rows.
+    const uint32_t rows_max = std::max(1u, d.max_batch), NS = std::min(d.V, SCORE_NS);
+    const size_t per_pos = (size_t)d.C * 4;
+    if (!m->d_score) DALLOC(m->d_score, 4 * per_pos + (size_t)rows_max * sizeof(ScoreState) + 256);
+    if (mfma && !m->d_score_slab) DALLOC(m->d_score_slab, (size_t)m->pf.T * NS * 4);
+    const Tensor &head = m->output.ptr ? m->output : m->token_embd;
+    if (mfma && head.type != NFAI_F16 && !m->d_score_wide) DALLOC(m->d_score_wide, (size_t)NS * d.E * 2);
+    char *base = static_cast<char *>(m->d_score);
+    uint32_t *d_tgt = reinterpret_cast<uint32_t *>(base);
+    float *d_lp = reinterpret_cast<float *>(base + per_pos);   // the three outputs of THIS call side by side, n words each: one download
+    uint32_t *d_am = reinterpret_cast<uint32_t *>(d_lp + n);
+    float *d_lpm = d_lp + 2 * (size_t)n;
+    ScoreState *state = reinterpret_cast<ScoreState *>(base + 4 * per_pos);
+    uint32_t *d_err = reinterpret_cast<uint32_t *>(base + 4 * per_pos + (size_t)rows_max * sizeof(ScoreState));
+    std::vector<uint32_t> tgt(n);
+    for (uint32_t i = 0; i < n; i++) tgt[i] = targets ? targets[i] : (i + 1 < n ? tokens[i + 1] : NFAI_SCORE_NO_TARGET);
+    HIP_TRY(hipMemcpyAsync(d_tgt, tgt.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_err, 0, 4, s));
+    if (mfma) {
+        S_TRY(ensure_wide_shadow(m));
+        for (uint32_t done = 0; done < n;) {
+            const uint32_t T = std::min(n - done, d.max_batch);
+            S_TRY(prefill_chunk(m, tokens + done, T));
+            S_TRY(score_chunk_head(m, T, d_tgt + done, state, d_err, d_lp + done, d_am + done, d_lpm + done));
+            done += T;
+        }
+        S_TRY(prefill_head(m));   // the last token's fp32 logits, ArgMax -> token word: where _prefill leaves the model
+    } else {
+        // the reference-exact form: per token the body of _decode_step (fp32 activations), the row kernels on its logits
+        for (uint32_t i = 0; i < n; i++) {
+            S_TRY(step_token_blocking(m, tokens[i]));
+            hipError_t e = launch_score_slab(m->logits, 1, d.V, 0, d.V, d.V, d_tgt + i, state, d_err, s);
+            if (e == hipSuccess) e = launch_score_finish(state, 1, d_tgt + i, d_err, d_lp + i, d_am + i, d_lpm + i, s);
+            if (e != hipSuccess) return fail(NFAI_ERR_HIP, "score: row launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    std::vector<uint32_t> out(3 * (size_t)n);   // one download: logprob | argmax | logprob_max of the n rows
+    HIP_TRY(hipMemcpyAsync(out.data(), d_lp, 3 * (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (logprob) memcpy(logprob, out.data(), (size_t)n * 4);
+    if (argmax) memcpy(argmax, out.data() + n, (size_t)n * 4);
+    if (logprob_max) memcpy(logprob_max, out.data() + 2 * (size_t)n, (size_t)n * 4);
+    return NFAI_OK;
 }
 
 // The prompt phase of one pipeline stage (LlamaModel.cs:103-126 sliced by layer_begin / layer_end): n prompt tokens' K / V rows,

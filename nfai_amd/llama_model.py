@@ -232,6 +232,27 @@ class LlamaModel:
         if t.size:
             call("nfai_hip_llama_ingest", self.handle, t.ctypes.data_as(C.POINTER(C.c_uint32)), t.size)
 
+    def Score(self, tokens, targets=None):
+        """Log-probabilities of every position (nfai_hip_llama_score): the tokens run at positions pos .. pos + n - 1 and leave their
+        K / V rows; row i scores targets[i] (None: tokens[i + 1], the last row nothing — its logprob is 0; _lib.SCORE_NO_TARGET: no
+        target on that row).  Returns (logprob[n] f32, argmax[n] u32, logprob_max[n] f32)."""
+        t = np.ascontiguousarray(tokens, np.uint32)
+        g = None if targets is None else np.ascontiguousarray(targets, np.uint32)
+        if g is not None and g.size != t.size:
+            raise ValueError(f"Score: {g.size} targets for {t.size} tokens")
+        lp, am, lpm = np.empty(t.size, np.float32), np.empty(t.size, np.uint32), np.empty(t.size, np.float32)
+        call("nfai_hip_llama_score", self.handle, t.ctypes.data_as(C.POINTER(C.c_uint32)), t.size,
+             None if g is None else g.ctypes.data_as(C.POINTER(C.c_uint32)), lp.ctypes.data_as(C.POINTER(C.c_float)),
+             am.ctypes.data_as(C.POINTER(C.c_uint32)), lpm.ctypes.data_as(C.POINTER(C.c_float)))
+        return lp, am, lpm
+
+    def Perplexity(self, tokens) -> float:
+        """exp(-mean log p(tokens[i + 1] | tokens[..i])) over the n - 1 predicted tokens (needs n >= 2)."""
+        lp, _, _ = self.Score(tokens)
+        if lp.size < 2:
+            raise ValueError("Perplexity: at least two tokens")
+        return float(np.exp(-np.mean(lp[:-1], dtype=np.float64)))
+
     def StageStep(self, token: int = 0, hidden_in: int | None = None, hidden_out: int | None = None, want_logits: bool = False,
                   want_argmax: bool = False):
         logits = np.empty(self.dims["V"], np.float32) if want_logits else None
