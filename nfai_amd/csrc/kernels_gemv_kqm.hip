@@ -17,7 +17,7 @@
 // signed base-256 digits; sum q * x' = S0 + 256 S1 + 65536 S2 is exact in int32, the K-quant scales
 // (d * sc, dmin * m, the -32 offset of Q6_K via the group sums of x') are applied in fp32 exactly
 // as ggml defines the block; Q8_0 (d * q, q a signed byte) needs neither sums nor offsets: one d per lane
-// and MFMA; Q4_0 (d * (q - 8), q a nibble) takes Q4_K's staging and sums of x' with d and 8 d in place of the scale and the min.  The only approximation is x' = round(x * 2^S): 24 bits relative to
+// and MFMA; Q4_0 (d * (q - 8), q a nibble) takes Q4_K's staging and sums of x' with d and 8 d in place of the scale and the min; Q3_K (d * (sc - 32) * (q - 4), q three bits) takes Q6_K's staging, its -4 through the per-16 sums of x' as Q6_K's -32.  The only approximation is x' = round(x * 2^S): 24 bits relative to
 // the largest |x| of the super-block.  Against the fp32 oracle the differences are at the level of
 // fp32 summation-order noise (tests/test_gpu_kquant.py states the tolerance; max |dlogit| 1.5e-5 at 3B).
 //
@@ -128,12 +128,13 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
     // QT = NFAI_Q8_0_T16: its own A-fragment layout, never mixed with the K-quants (llama.hip gives a Q8_0 segment its own launch).
     // QT = NFAI_Q5_K_T16: the Q4_K staging (fragments and sums of x'); NFAI_KQ_MIXED5: Q5_K and Q6_K segments as NFAI_KQ_MIXED.
     // QT = NFAI_Q4_0_T16: the Q4_K staging too (t16.h); launched on Q4_0 segments only (llama.hip gives them their own launch).
-    constexpr bool HAS8 = QT == NFAI_Q8_0_T16, HAS5 = QT == NFAI_Q5_K_T16 || QT == NFAI_KQ_MIXED5, IS40 = QT == NFAI_Q4_0_T16;
-    constexpr bool HAS4 = !HAS8 && QT != NFAI_Q6_K_T16, HAS6 = !HAS8 && !IS40 && QT != NFAI_Q4_K_T16 && QT != NFAI_Q5_K_T16, MIXED = HAS4 && HAS6;
+    // QT = NFAI_Q3_K_T16: the Q6_K staging (fragments and per-16 sums of x', t16.h); launched on Q3_K segments only, as Q4_0.
+    constexpr bool HAS8 = QT == NFAI_Q8_0_T16, HAS5 = QT == NFAI_Q5_K_T16 || QT == NFAI_KQ_MIXED5, IS40 = QT == NFAI_Q4_0_T16, IS3 = QT == NFAI_Q3_K_T16;
+    constexpr bool HAS4 = !HAS8 && !IS3 && QT != NFAI_Q6_K_T16, HAS6 = !HAS8 && !IS40 && QT != NFAI_Q4_K_T16 && QT != NFAI_Q5_K_T16, MIXED = HAS4 && HAS6;
     static_assert(!MIXED || MODE == GEMV_QKV_ROPE, "mixed encodings exist for the q|k|v launch only");
     using Regs = typename std::conditional<
         QT == NFAI_Q4_K_T16, Q4T,
-        typename std::conditional<HAS8, Q8T, typename std::conditional<QT == NFAI_Q5_K_T16, Q5T, typename std::conditional<IS40, Q40T, Q6T>::type>::type>::type>::type;
+        typename std::conditional<HAS8, Q8T, typename std::conditional<QT == NFAI_Q5_K_T16, Q5T, typename std::conditional<IS40, Q40T, typename std::conditional<IS3, Q3T, Q6T>::type>::type>::type>::type>::type;
     constexpr int R = MODE == GEMV_GATEUP ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x, lane = tid & 63, nw = blockDim.x >> 6;
@@ -203,6 +204,8 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
             buf = q5t_load(p, seg, tile, blk, lane);
         } else if constexpr (IS40) {
             buf = q40t_load(p, seg, tile, blk, lane);
+        } else if constexpr (IS3) {
+            buf = q3t_load(p, seg, tile, blk, lane);
         } else {
             if ((p.seg6 >> seg) & 1u) {
                 buf = q6t_load(p, seg, tile, blk, lane);
@@ -269,7 +272,7 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
         const uint32_t bc = wid * BPW + bi;
         const bool live = bc < p.NB;
         const uint32_t blk = min(bc, p.NB - 1);
-        bool is6 = QT == NFAI_Q6_K_T16;
+        bool is6 = QT == NFAI_Q6_K_T16 || IS3;  // the Q6_K staging
         if constexpr (MIXED) {
             uint32_t seg, tile;
             kqm_unit<MODE>(p, blockIdx.x + ui * gridDim.x, tt, seg, tile);
@@ -290,7 +293,8 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
             if (is6) {
                 if constexpr (HAS6) {
                     const f32x4 sm = *reinterpret_cast<const f32x4 *>(sums6 + (blk * 4 + g) * 4);
-                    a = q6t_dot(buf, af, sm, g);
+                    if constexpr (IS3) a = q3t_dot(buf, af, sm, g);
+                    else a = q6t_dot(buf, af, sm, g);
                 }
             } else {
                 if constexpr (HAS4) {
@@ -489,6 +493,31 @@ __global__ void k_repack_q40_t16(const uint8_t *src, uint8_t *dst, uint32_t n_ti
     }
 }
 
+// ---- Q3_K repack: native 110-byte blocks (row-major: hmask[32], qs[64], scales[12], d) -> T16 planes (same bytes) --------------------
+// Plane 0: the lane's 16 qs bytes as they are; plane 1: the bit order of t16.h; planes 2 and 3: the scale bytes and d as they are.
+__global__ void k_repack_q3k_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
+{
+    const uint64_t tb = blockIdx.x;
+    const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB), t = threadIdx.x;
+    const uint64_t nblk = t16_nblk(n_tiles, NB);
+    // native blocks are only 2-byte aligned: byte copies
+    for (uint32_t e = t; e < 1024; e += blockDim.x) {
+        const uint32_t ln = e >> 4, b = e & 15, G = ln >> 4, r = ln & 15, n = G >> 1, lh = G & 1;
+        t16_q3k_qs(dst, tb)[e] = src[((uint64_t)(tile * 16 + r) * NB + blk) * GGML_Q3_K_BLOCK + 32 + 32 * n + 16 * lh + b];
+    }
+    for (uint32_t e = t; e < 512; e += blockDim.x) {  // byte b of word w of lane ln: weights l = 8w + 4 i2 + b, bit 4 i2 + j
+        const uint32_t ln = e >> 3, w = (e >> 2) & 1, b = e & 3, G = ln >> 4, r = ln & 15, n = G >> 1, lh = G & 1;
+        const uint8_t *hm = src + ((uint64_t)(tile * 16 + r) * NB + blk) * GGML_Q3_K_BLOCK + 16 * lh;
+        uint32_t byte = 0;
+        for (uint32_t i2 = 0; i2 < 2; i2++)
+            for (uint32_t j = 0; j < 4; j++) byte |= ((hm[8 * w + 4 * i2 + b] >> (4 * n + j)) & 1u) << (4 * i2 + j);
+        t16_q3k_hm(dst, nblk, tb)[e] = (uint8_t)byte;
+    }
+    for (uint32_t e = t; e < 192; e += blockDim.x)
+        t16_q3k_sc(dst, nblk, tb)[e] = src[((uint64_t)(tile * 16 + e / 12) * NB + blk) * GGML_Q3_K_BLOCK + 96 + e % 12];
+    if (t < 32) t16_q3k_d(dst, nblk, tb)[t] = src[((uint64_t)(tile * 16 + (t >> 1)) * NB + blk) * GGML_Q3_K_BLOCK + 108 + (t & 1)];
+}
+
 // ---- Q5_K repack: native 176-byte blocks (row-major: d, dmin, scales[12], qh[32], qs[128]) -> T16 planes -------------------
 // Planes 0 and 1 as k_repack_q4k_t16 (qs at byte 48 of the block, the header is its first 16 bytes); plane 2: the bit order of t16.h.
 __global__ void k_repack_q5k_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
@@ -536,6 +565,10 @@ hipError_t launch_repack_q5k_t16(const void *native, void *tiled, uint64_t rows,
 hipError_t launch_repack_q40_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
 {
     return launch_repack_t16(k_repack_q40_t16, 256, native, tiled, rows, cols, s);
+}
+hipError_t launch_repack_q3k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
+{
+    return launch_repack_t16(k_repack_q3k_t16, 256, native, tiled, rows, cols, s);
 }
 
 // ---- rows of a T16 table -> fp32 (embedding gather): row tok[t] to y + t * E (prefill, single token) or, y == nullptr, to x[t] (the
@@ -651,6 +684,29 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
                 *reinterpret_cast<f16x8 *>(orow + (2 * g + h) * 32 + c * 8) = o;
             }
         }
+    } else if constexpr (QT == NFAI_Q3_K_T16) {
+        const u32x4 q = load_nt16(t16_q3k_qs(W, tb) + lane * 16);
+        const u32x2 hm = *reinterpret_cast<const u32x2 *>(t16_q3k_hm(W, nblk, tb) + lane * 8);
+        const uint32_t *scw = reinterpret_cast<const uint32_t *>(t16_q3k_sc(W, nblk, tb) + r * 12);
+        const uint32_t s0 = scw[0], s1 = scw[1], s2 = scw[2];
+        const float d = (float)*reinterpret_cast<const _Float16 *>(t16_q3k_d(W, nblk, tb) + r * 2);
+        const uint32_t n = g >> 1, lh = g & 1;
+#pragma unroll
+        for (int qd = 0; qd < 4; qd++) {  // weights 128n + 32qd + 16lh .. +16 of row r: (d * (sc - 32)) * (q - 4), as ggml writes it
+            const float dl = d * (float)(q3k_scale(s0, s1, s2, 8 * n + lh + 2 * qd) - 32);
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                f16x8 o;
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    const uint32_t l = c * 8 + e;  // byte l & 3 of dword l >> 2; its high bit at 8 (l & 3) + 4 ((l >> 2) & 1) + qd of word l >> 3
+                    const uint32_t lo = (q[l >> 2] >> (8 * (l & 3) + 2 * qd)) & 3u;
+                    const uint32_t hb = (hm[l >> 3] >> (8 * (l & 3) + 4 * ((l >> 2) & 1) + qd)) & 1u;
+                    o[e] = f16_of_f32(dl * (float)((int)(lo | (hb << 2)) - 4));
+                }
+                *reinterpret_cast<f16x8 *>(orow + n * 128 + qd * 32 + lh * 16 + c * 8) = o;
+            }
+        }
     } else if constexpr (QT == NFAI_Q8_0_T16) {
         const u32x4 dv = load_nt16(t16_q80_d(W, nblk, tb) + r * 16);
 #pragma unroll
@@ -713,6 +769,7 @@ hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64
     else if (type == NFAI_Q6_K_T16) NFAI_DQ(NFAI_Q6_K_T16);
     else if (type == NFAI_Q5_K_T16) NFAI_DQ(NFAI_Q5_K_T16);
     else if (type == NFAI_Q4_0_T16) NFAI_DQ(NFAI_Q4_0_T16);
+    else if (type == NFAI_Q3_K_T16) NFAI_DQ(NFAI_Q3_K_T16);
     else if (type == NFAI_Q8_0_T16) NFAI_DQ(NFAI_Q8_0_T16);
     else return hipErrorInvalidValue;
 #undef NFAI_DQ
@@ -869,6 +926,7 @@ hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s)
     if (a.w_type == NFAI_Q5_K_T16) return q4t_mode<NFAI_Q5_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     if (a.w_type == NFAI_Q8_0_T16) return q4t_mode<NFAI_Q8_0_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     if (a.w_type == NFAI_Q4_0_T16) return q4t_mode<NFAI_Q4_0_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
+    if (a.w_type == NFAI_Q3_K_T16) return q4t_mode<NFAI_Q3_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     if (a.w_type == NFAI_Q4_K_T16) return q4t_mode<NFAI_Q4_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     return q4t_mode<NFAI_Q6_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
 }

@@ -44,6 +44,7 @@ struct Q8T { u32x4 q[4]; u32x2 d; };
 struct Q5T { u32x4 q0, q1, hdr; u32x2 qh; };
 struct Q6T { u32x4 qla, qlb, qh, sc; uint32_t d; };
 struct Q40T { u32x4 q0, q1; uint32_t d; };
+struct Q3T { u32x4 q; u32x2 h; uint32_t s0, s1, s2, d; };
 
 __device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t mask, uint32_t bits) { return (a & mask) | bits; }
 
@@ -287,8 +288,65 @@ __device__ __forceinline__ float q6t_dot(const Q6T &w, const i32x4 (&af)[4], f32
     return d * tot;
 }
 
+// One step of a wave on a Q3_K T16 tensor: the low bits (1 KiB), the high bits (512 B), the 16 rows' scale bytes (192 B) and d (32 B) of
+// tile-block tb: 1760 bytes, 10 VGPRs per step.
+__device__ __forceinline__ Q3T q3t_load_raw(const uint8_t *base, uint64_t n_tiles, uint32_t NB, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    const uint64_t tb = t16_tb(tile, NB, blk), nblk = t16_nblk(n_tiles, NB);
+    Q3T r;
+    r.q = load_nt16(t16_q3k_qs(base, tb) + lane * 16);
+    r.h = __builtin_nontemporal_load((const GLOBAL_AS u32x2 *)(t16_q3k_hm(base, nblk, tb) + lane * 8));
+    const GLOBAL_AS uint32_t *sc = (const GLOBAL_AS uint32_t *)(t16_q3k_sc(base, nblk, tb) + (lane & 15) * 12);
+    r.s0 = __builtin_nontemporal_load(sc);
+    r.s1 = __builtin_nontemporal_load(sc + 1);
+    r.s2 = __builtin_nontemporal_load(sc + 2);
+    r.d = *reinterpret_cast<const GLOBAL_AS uint16_t *>(t16_q3k_d((const GLOBAL_AS uint8_t *)base, nblk, tb) + (lane & 15) * 2);
+    return r;
+}
+
+__device__ __forceinline__ Q3T q3t_load(const KqmParams &p, uint32_t seg, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    return q3t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
+}
+
+// The B operand of quarter qd of a Q3_K step, one unsigned byte q + BIAS per weight (q = low two bits | high bit << 2, 0..7): dword i takes
+// its low bits with one shift and mask of w.q[i], its four high bits with one shift of word i >> 1 of w.h (bit 8b + 4 (i & 1) + qd -> 8b + 2)
+// and one v_and_or_b32.  BIAS (a byte value, no carry: q + BIAS < 256) is added per dword when not zero.
+template <uint32_t BIAS>
+__device__ __forceinline__ i32x4 q3t_operand(const Q3T &w, int qd)
+{
+    constexpr uint32_t M2 = 0x03030303u, B = 0x04040404u;
+    u32x4 b;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t h = w.h[i >> 1];
+        const int c = 4 * (i & 1) + qd;  // the bit's place in each byte of h
+        b[i] = and_or(c >= 2 ? h >> (c - 2) : h << (2 - c), B, (w.q[i] >> (2 * qd)) & M2);
+        if constexpr (BIAS != 0) b[i] += BIAS * 0x01010101u;
+    }
+    return __builtin_bit_cast(i32x4, b);
+}
+
+// 64 weights of one lane: Q6_K's ownership (half n = G>>1 of the super-block, columns l = 16*(G&1) .. +15 of all four quarters), so the
+// activations are Q6_K's A fragments and per-16 sums of x' (kqm_stage<HAS6>); one MFMA per quarter = one 16-weight scale group on
+// unsigned 3-bit byte operands.  Weight = d * (sc - 32) * (q - 4): the -4 goes through the group's sum of x', the 6-bit scale
+// (q3k_scale) is applied as an integer-valued float, d last: d * sum (sc - 32) * (v - 4 * sums[qd]).
+__device__ __forceinline__ float q3t_dot(const Q3T &w, const i32x4 (&af)[4], f32x4 sums, uint32_t g)
+{
+    const float d = h2f_lo(w.d);
+    float tot = 0.f;
+#pragma unroll
+    for (int qd = 0; qd < 4; qd++) {
+        const i32x4 dq = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[qd], q3t_operand<0>(w, qd), i32x4{0, 0, 0, 0}, 0, 0, 0);
+        const float v = fmaf((float)dq[2], 65536.0f, fmaf((float)dq[1], 256.0f, (float)dq[0]));
+        const int sc = q3k_scale(w.s0, w.s1, w.s2, 8 * (g >> 1) + (g & 1) + 2 * qd) - 32;  // scale[8n + 2 qd + lh] of the row
+        tot = fmaf((float)sc, fmaf(-4.0f, sums[qd], v), tot);
+    }
+    return d * tot;
+}
+
 // ---- a step against several activation vectors (the batched decode): unpack once, then one dot per column ------------------------------
-// The part of q4t_dot / q5t_dot / q6t_dot / q8t_dot / q40t_dot that does not depend on x, done once per step: the four B operands (one byte per
+// The part of q4t_dot / q5t_dot / q6t_dot / q8t_dot / q40t_dot / q3t_dot that does not depend on x, done once per step: the four B operands (one byte per
 // weight) and the scales.
 struct KqmW4 { i32x4 b[4]; float scv[2], mv[2]; };   // b[2n + hf]: low (n = 0) / high (n = 1) nibbles of q{hf}, the slot order of the A fragments
 struct KqmW6 { i32x4 b[4]; float sc[4]; float d; };  // b[qd], scales[8n + (G&1) + 2 qd] as floats
@@ -327,6 +385,20 @@ __device__ __forceinline__ KqmW6 kqm_unpack(const Q6T &w, uint32_t g)
         const uint32_t si = 8 * (g >> 1) + (g & 1) + 2 * qd;
         const uint32_t sw = si < 8 ? (si < 4 ? w.sc[0] : w.sc[1]) : (si < 12 ? w.sc[2] : w.sc[3]);
         u.sc[qd] = (float)(int)(int8_t)((sw >> ((si & 3) * 8)) & 0xFFu);
+    }
+    return u;
+}
+
+// Q3_K: the operand of Q6_K's columns.  The bytes carry q + 28 (28..35, still an unsigned 6-bit value), so that the -32 of
+// kqm_dot(KqmW6) leaves q - 4: no offset field in KqmW6, and Q6_K's column dot is untouched.  sc[qd] = scale - 32 as a float.
+__device__ __forceinline__ KqmW6 kqm_unpack(const Q3T &w, uint32_t g)
+{
+    KqmW6 u;
+    u.d = h2f_lo(w.d);
+#pragma unroll
+    for (int qd = 0; qd < 4; qd++) {
+        u.b[qd] = q3t_operand<28>(w, qd);
+        u.sc[qd] = (float)(q3k_scale(w.s0, w.s1, w.s2, 8 * (g >> 1) + (g & 1) + 2 * qd) - 32);
     }
     return u;
 }
@@ -437,7 +509,7 @@ __device__ __forceinline__ float kqm_dot(const KqmW8 &u, const i32x4 (&af)[4], f
 
 // Fixed-point staging of ONE 256-element super-block of the activation vector by one wave (lane holds elements 4*lane .. +3, after the
 // optional RMSNorm): power-of-two scale so that |x * 2^S| < 2^22, three signed base-256 digits per element written as MFMA A
-// fragments [blk][slot:4][G][digit][16 B] (Q4_K / Q5_K layout in xa, Q6_K layout in xa6, Q8_0 layout in xa), the sums of x' per scale group
+// fragments [blk][slot:4][G][digit][16 B] (Q4_K / Q5_K / Q4_0 layout in xa, Q6_K / Q3_K layout in xa6, Q8_0 layout in xa), the sums of x' per scale group
 // (K-quants only) and the exponent S (sexp[blk]; the consumer applies ldexpf(partial, -S)).  Nothing written here is read by another wave.
 // S = 21 - ilogb(max|x|) for every finite non-zero maximum, fp32 subnormals (S up to 170) to FLT_MAX (S = -106) alike, and x is scaled
 // with ldexpf on the value, so neither 2^S nor 2^-S is ever formed as a float: every finite super-block keeps 22+ bits of its maximum.
@@ -468,7 +540,7 @@ __device__ __forceinline__ void kqm_stage(const f32x4 v, const uint32_t blk, con
     }
     // A fragments [blk][slot:4][G][digit][16 bytes]; a lane reads slot s at +256*s from its (G, digit) base.
     //   Q4_K: k = (2G+n)*32 + hf*16 + j, slot = 2n + hf, sums per sub-block of 32 -> [blk][G][n]
-    //   Q6_K: k = n*128 + qd*32 + lh*16 + j, G = 2n + lh, slot = qd, sums per group of 16 -> [blk][G][qd]
+    //   Q6_K, Q3_K: k = n*128 + qd*32 + lh*16 + j, G = 2n + lh, slot = qd, sums per group of 16 -> [blk][G][qd]
     //   Q8_0: k = 64*slot + 16G + j, no sums
     const uint32_t j = k & 15;
     // sums over aligned groups of 4 lanes (16 elements) and of 8 lanes (32 elements)

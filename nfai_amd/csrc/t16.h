@@ -1,4 +1,4 @@
-// t16.h — the "T16" layout of ggml Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 tensors in HBM: what it is, where every plane's bytes are, and how a
+// t16.h — the "T16" layout of ggml Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 tensors in HBM: what it is, where every plane's bytes are, and how a
 // block decodes.  The ONE definition: the repack kernels write it, the int8-MFMA GEMVs (kqm.h), the fp16 widening, the dequant-in-LDS
 // GEMM and the embedding gather read it, all through the helpers below.  Part of common.h (included there, behind the vector types
 // and load helpers it uses): include common.h, never this file alone.
@@ -28,18 +28,28 @@
 //                  32-blocks 2G and 2G+1 as it owns sub-blocks 2G and 2G+1 of a Q4_K block: Q4_K's register shape per step;
 //         plane 1  [tile][blk][r:16][16 B]          the eight fp16 d of that row and super-block in block order: lanes of group G read
 //                                                   dword G, the d of their 32-blocks 2G (low half) and 2G+1 (high half).
-// Every wave-wide load is one contiguous kilobyte (quants), 512 bytes (Q5_K high bits) or 256 bytes (headers).
+//   Q3_K: plane 0  [tile][blk][lane:64][16 B]       lane = G*16 + r, n = G>>1, lh = G&1, holds qs[32n + 16lh .. +16) of row 16*tile+r: bits 2j..2j+1
+//                  of byte l are the low two bits of weight 128n + 32j + 16lh + l, so ONE load gives the lane all four quarters j of the
+//                  64 weights it owns (Q6_K's ownership: group G, A-fragment slot j of kqm_stage<HAS6>);
+//         plane 1  [tile][blk][lane:64][8 B]        the 64 high bits (hmask) of exactly those weights, in the order of q3t_dot (kqm.h): one
+//                  shift and one v_and_or_b32 per four weights.  Word w of lane (G, r) holds, for the weights l = 8w + 4i2 + b (b = byte of
+//                  operand dword i = 2w + i2) of quarter j, bit 4n + j of hmask[16lh + l] at 8b + 4 i2 + j;
+//         plane 2  [tile][blk][r:16][12 B]          the 12 scale bytes of row 16*tile+r (sixteen 6-bit scales, q3k_scale);
+//         plane 3  [tile][blk][r:16] fp16           d.
+// Every wave-wide load is one contiguous kilobyte (quants), 512 bytes (Q5_K / Q3_K high bits), 256 bytes (headers) or 192 bytes (Q3_K scales).
 // (The planar Q6_K layout of kernels_gemv_kq.hip, for row counts that are not a multiple of 16, is another format.)
 #pragma once
 
 namespace nfai {
 
 // Bytes per row and super-block of every plane: the native ggml block, split up.
-constexpr uint32_t GGML_Q4_K_BLOCK = 144, GGML_Q5_K_BLOCK = 176, GGML_Q6_K_BLOCK = 210, GGML_Q8_0_BLOCK = 34, GGML_Q4_0_BLOCK = 18;
+constexpr uint32_t GGML_Q4_K_BLOCK = 144, GGML_Q5_K_BLOCK = 176, GGML_Q6_K_BLOCK = 210, GGML_Q8_0_BLOCK = 34, GGML_Q4_0_BLOCK = 18, GGML_Q3_K_BLOCK = 110;
 constexpr uint32_t T16_K4_QS = 128, T16_K4_HDR = 16, T16_Q5K_QH = 32;  // Q4_K / Q5_K: qs | d, dmin, scales[12] | qh
 constexpr uint32_t T16_Q6K_Q = 192, T16_Q6K_SC = 16, T16_Q6K_D = 2;    // Q6_K: ql[128] + qh[64] | scales[16] | d
 constexpr uint32_t T16_Q80_QS = 256, T16_Q80_D = 16;                   // Q8_0: 8 x qs[32] | 8 x d
 constexpr uint32_t T16_Q40_QS = 128, T16_Q40_D = 16;                   // Q4_0: 8 x qs[16] | 8 x d
+constexpr uint32_t T16_Q3K_QS = 64, T16_Q3K_HM = 32, T16_Q3K_SC = 12, T16_Q3K_D = 2;  // Q3_K: qs[64] | hmask[32] | scales[12] | d
+static_assert(T16_Q3K_QS + T16_Q3K_HM + T16_Q3K_SC + T16_Q3K_D == GGML_Q3_K_BLOCK, "the T16 planes are the bytes of the native blocks (weight_row_bytes)");
 static_assert(T16_Q40_QS + T16_Q40_D == 8 * GGML_Q4_0_BLOCK, "the T16 planes are the bytes of the native blocks (weight_row_bytes)");
 static_assert(T16_K4_QS + T16_K4_HDR == GGML_Q4_K_BLOCK && T16_K4_QS + T16_K4_HDR + T16_Q5K_QH == GGML_Q5_K_BLOCK &&
                   T16_Q6K_Q + T16_Q6K_SC + T16_Q6K_D == GGML_Q6_K_BLOCK && T16_Q80_QS + T16_Q80_D == 8 * GGML_Q8_0_BLOCK,
@@ -61,6 +71,10 @@ T16_ADDR t16_q80_qs(P base, uint64_t tb) { return base + tb * (16 * T16_Q80_QS);
 T16_ADDR t16_q80_d(P base, uint64_t nblk, uint64_t tb) { return base + nblk * T16_Q80_QS + tb * (16 * T16_Q80_D); }                // + r * 16
 T16_ADDR t16_q40_qs(P base, uint64_t tb) { return base + tb * (16 * T16_Q40_QS); }                                                 // + h * 1024 + lane * 16
 T16_ADDR t16_q40_d(P base, uint64_t nblk, uint64_t tb) { return base + nblk * T16_Q40_QS + tb * (16 * T16_Q40_D); }                // + r * 16
+T16_ADDR t16_q3k_qs(P base, uint64_t tb) { return base + tb * (16 * T16_Q3K_QS); }                                                 // + lane * 16
+T16_ADDR t16_q3k_hm(P base, uint64_t nblk, uint64_t tb) { return base + nblk * T16_Q3K_QS + tb * (16 * T16_Q3K_HM); }              // + lane * 8
+T16_ADDR t16_q3k_sc(P base, uint64_t nblk, uint64_t tb) { return base + nblk * (T16_Q3K_QS + T16_Q3K_HM) + tb * (16 * T16_Q3K_SC); }  // + r * 12
+T16_ADDR t16_q3k_d(P base, uint64_t nblk, uint64_t tb) { return base + nblk * (T16_Q3K_QS + T16_Q3K_HM + T16_Q3K_SC) + tb * (16 * T16_Q3K_D); }  // + r * 2
 #undef T16_ADDR
 
 // ---- block decode ------------------------------------------------------------------------------------------------------------------
@@ -90,8 +104,18 @@ __device__ __forceinline__ int q6k_scale(const u32x4 sc, uint32_t si)
     return (int)(int8_t)((sw >> ((si & 3) * 8)) & 0xFFu);
 }
 
+// Q3_K: the 6-bit scale (0..63; the weight's factor is scale - 32) of 16-weight group si (0..15) from the three scale words of the
+// block: low nibble = nibble si >> 3 of byte si & 7, high two bits = bits 2 (si >> 2) .. + 1 of byte 8 + (si & 3).
+__device__ __forceinline__ int q3k_scale(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t si)
+{
+    const uint32_t lw = (si & 4) ? s1 : s0;
+    const uint32_t lo = (lw >> (8 * (si & 3) + 4 * (si >> 3))) & 0xFu;
+    const uint32_t hi = (s2 >> (8 * (si & 3) + 2 * (si >> 2))) & 3u;
+    return (int)(lo | (hi << 4));
+}
+
 // Four consecutive elements k .. k+3 (k % 4 == 0) of row `row` of a T16 tensor with E columns and n_rows rows, as fp32: the block
-// exactly as ggml dequantises it (d * sc * q - dmin * m; d * sc * (q - 32); d * q; d * (q - 8)), products and the difference rounded as written.
+// exactly as ggml dequantises it (d * sc * q - dmin * m; d * sc * (q - 32); d * q; d * (q - 8); (d * (sc - 32)) * (q - 4)), products and the difference rounded as written.
 __device__ __forceinline__ f32x4 t16_row_load4(const uint8_t *table, int type, uint64_t n_rows, uint64_t row, uint32_t k, uint32_t E)
 {
     typedef __attribute__((address_space(1))) uint8_t g8;
@@ -114,6 +138,22 @@ __device__ __forceinline__ f32x4 t16_row_load4(const uint8_t *table, int type, u
         for (int e = 0; e < 4; e++) {
             const uint32_t q = (q4 >> (8 * e)) & 0xFFu;
             out[e] = d * (float)((int)((l >> 4) ? (q >> 4) : (q & 0xFu)) - 8);
+        }
+    } else if (type == NFAI_Q3_K_T16) {
+        const uint32_t n = kk >> 7, j = (kk >> 5) & 3, lh = (kk >> 4) & 1, l = kk & 15;  // l % 4 == 0: the four weights are one operand dword
+        const uint32_t ln = (n * 2 + lh) * 16 + (uint32_t)r;
+        const uint32_t q4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t16_q3k_qs(t, tb) + ln * 16 + l);
+        const uint32_t h4 = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(t16_q3k_hm(t, nblk, tb) + ln * 8 + (l >> 3) * 4) >>
+                            (4 * ((l >> 2) & 1) + j);  // the high bits of the four weights at bits 8e
+        const g8 *scb = t16_q3k_sc(t, nblk, tb) + r * 12;
+        const uint32_t si = 8 * n + 2 * j + lh;  // the scale as q3k_scale forms it, on the two bytes that hold it
+        const int sc = (int)(((scb[si & 7] >> (4 * (si >> 3))) & 0xFu) | (((scb[8 + (si & 3)] >> (2 * (si >> 2))) & 3u) << 4));
+        const float d = (float)reinterpret_cast<const __attribute__((address_space(1))) _Float16 *>(t16_q3k_d(t, nblk, tb))[r];
+        const float dl = d * (float)(sc - 32);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int q = (int)(((q4 >> (8 * e + 2 * j)) & 3u) | (((h4 >> (8 * e)) & 1u) << 2)) - 4;
+            out[e] = dl * (float)q;
         }
     } else if (type == NFAI_Q4_K_T16 || type == NFAI_Q5_K_T16) {
         const uint32_t sb = kk >> 5, l = kk & 31;

@@ -141,6 +141,101 @@ def q4_0_type(name: str, dims, mix: str = "q4_0") -> int:
     return 2
 
 
+def _q3_k_scales(b):
+    """The sixteen 6-bit scales (0..63) of every Q3_K block in b [nb][110]: low nibble of scale i from scales[i] (i < 8) or the
+    high nibble of scales[i - 8], its high two bits from bits 2 (i // 4) .. + 1 of scales[8 + i % 4]."""
+    s = b[:, 96:108]
+    lo = np.concatenate([s[:, 0:8] & 0xF, s[:, 0:8] >> 4], axis=1)                            # [nb][16]
+    i = np.arange(16)
+    hi = (s[:, 8 + i % 4] >> (2 * (i // 4))[None, :]) & 3
+    return (lo | (hi << 4)).astype(np.int32)
+
+
+def dequantize_q3_k(raw, rows: int, cols: int) -> np.ndarray:
+    """ggml block_q3_K (hmask[32], qs[64], scales[12], fp16 d per 256 weights) dequantised as restated from the format: float32
+    [rows][cols].  Element k = 128 n + 32 j + 16 lh + l has low bits (qs[32 n + 16 lh + l] >> 2 j) & 3, high bit
+    (hmask[16 lh + l] >> (4 n + j)) & 1 and scale index 8 n + 2 j + lh; y = dl * q with dl = d * (scale - 32) and
+    q = low + 4 high - 4, both products rounded to fp32.  The restatement was written without ggml's source at hand: check it
+    against a real Q3_K file when one is available."""
+    b = np.frombuffer(bytes(raw), np.uint8).reshape(-1, 110)
+    nb = b.shape[0]
+    d = b[:, 108:110].copy().view(np.float16).astype(np.float32)                              # [nb][1]
+    dl = (d * (_q3_k_scales(b) - 32).astype(np.float32)).astype(np.float32)                   # [nb][16], index 8 n + 2 j + lh
+    qs = b[:, 32:96].reshape(nb, 2, 1, 32)                                                    # [nb][n][.][16 lh + l]
+    hm = b[:, 0:32].reshape(nb, 1, 1, 32)
+    n = np.arange(2).reshape(1, 2, 1, 1)
+    j = np.arange(4).reshape(1, 1, 4, 1)
+    q = ((qs >> (2 * j)) & 3).astype(np.int32) + 4 * ((hm >> (4 * n + j)) & 1).astype(np.int32) - 4   # [nb][n][j][32]
+    y = dl.reshape(nb, 2, 4, 2, 1) * q.reshape(nb, 2, 4, 2, 16).astype(np.float32)
+    return y.astype(np.float32).reshape(rows, cols)
+
+
+def quantize_q3_k(W) -> bytes:
+    """Valid ggml block_q3_K for every row of W [rows][cols] (cols % 256 == 0): 110 bytes per 256 weights in the order hmask[32],
+    qs[64], scales[12], fp16 d.  NOT llama.cpp's quantiser bit for bit (its scale search is not restated).  Per group of 16 the
+    signed scale is s = -m / 4 with m the value of largest magnitude with its sign (the first among equals), so that the extreme
+    lands on code 0 (q - 4 = -4); d = max|s| / 31 as the next fp16 at or above it; the 6-bit scale is s / d rounded AWAY from zero
+    (never more than 31 in magnitude, as d was rounded up) + 32, and q = clip(rint(x / (d (sc - 32))), -4, 3) + 4.  With the step
+    |d (sc - 32)| >= |s| every |x| of the group is at most 4 steps, so only code +4 is clipped and every weight decodes within one
+    step |d (sc - 32)| of its value (nearest rounding of the scale would let a value of the extreme's magnitude and the other sign
+    miss that bound).  An all-zero block stores d = 0.  A fixed point on its own output, dequantize(quantize(y)) == y for
+    y = dequantize(quantize(W)), wherever every group has its extreme on code 0: that is every group whose scale is at least 8 in
+    magnitude (|s| / step > 7 / 8), and the block's largest group always (scale 31: d comes back exactly)."""
+    x = np.asarray(W, dtype=np.float32).reshape(-1, 16, 16)                                   # [nb][group 8 n + 2 j + lh][l]
+    nb = x.shape[0]
+    idx = np.argmax(np.abs(x), axis=2)
+    m = np.take_along_axis(x, idx[:, :, None], axis=2)[:, :, 0]
+    s = (m / np.float32(-4)).astype(np.float32)
+    d = _f16_up(np.abs(s).max(axis=1) / np.float32(31))
+    d32 = d.astype(np.float32)
+    ok = d32 > 0
+    k = np.where(ok[:, None], np.ceil(np.abs(s) / np.where(ok, d32, 1)[:, None]), 0).astype(np.float32)
+    k = np.minimum(k + (d32[:, None] * k < np.abs(s)), 31)                                    # (a quotient rounded down onto an integer)
+    sc = (np.sign(s) * k).astype(np.int32)
+    step = d32[:, None] * sc.astype(np.float32)                                               # d * (sc - 32) as the decoder forms it
+    q = np.where(step[:, :, None] != 0, np.rint(x / np.where(step != 0, step, 1)[:, :, None]), 0)
+    q = (np.clip(q, -4, 3) + 4).astype(np.uint8)                                              # [nb][16][16], codes 0..7
+    sc6 = (sc + 32).astype(np.uint8)
+    out = np.zeros((nb, 110), np.uint8)
+    q5 = q.reshape(nb, 2, 4, 2, 16)                                                           # [nb][n][j][lh][l]
+    for n in range(2):
+        for j in range(4):
+            code = q5[:, n, j].reshape(nb, 32)                                                # index 16 lh + l
+            out[:, 32 + 32 * n:64 + 32 * n] |= (code & 3) << (2 * j)
+            out[:, 0:32] |= (code >> 2) << (4 * n + j)
+    out[:, 96:104] = (sc6[:, 0:8] & 0xF) | ((sc6[:, 8:16] & 0xF) << 4)
+    for i in range(16):
+        out[:, 104 + i % 4] |= (sc6[:, i] >> 4) << (2 * (i // 4))
+    out[:, 108:110] = d.view(np.uint8).reshape(nb, 2)
+    return out.tobytes()
+
+
+def q3_k_type(name: str, dims, mix: str = "q3_k_m", layer_offset: int = 0, n_layers_file: int | None = None) -> int:
+    """ggml type of a matrix in a file of the Q3_K family.  mix="q3_k_m": attn_q, attn_k, ffn_gate, ffn_up in Q3_K (11); attn_v in
+    Q5_K (13) in the first two blocks, else Q4_K (12); attn_output in Q4_K; ffn_down in Q5_K in the first n_layer // 16 blocks, else
+    Q4_K; the lm_head (output.weight, or a tied token_embd) in Q6_K (14); an untied token_embd in Q3_K.  This is llama.cpp's rule
+    for the file type as recalled: its source was not at hand when this was written, so check it against a real file before relying
+    on it.  mix="q3_k_s": Q3_K everywhere but the Q6_K head.  mix="all_q3_k": every matrix Q3_K, the head and the embedding table
+    too (so that the Q3_K lm_head + ArgMax and embedding gather run).  layer_offset / n_layers_file: a pipeline stage's blocks
+    numbered within the whole file."""
+    if mix == "all_q3_k":
+        return 11
+    if mix not in ("q3_k_m", "q3_k_s"):
+        raise ValueError(f"unknown Q3_K mix {mix!r} (q3_k_m, q3_k_s, all_q3_k)")
+    if name == "output.weight" or (name == "token_embd.weight" and dims.tied):
+        return 14
+    if mix == "q3_k_s" or not name.startswith("blk."):
+        return 11
+    layer, n_layer = int(name.split(".")[1]) + layer_offset, n_layers_file or dims.L
+    if name.endswith("attn_v.weight"):
+        return 13 if layer < 2 else 12
+    if name.endswith("attn_output.weight"):
+        return 12
+    if name.endswith("ffn_down.weight"):
+        return 13 if layer < n_layer // 16 else 12
+    return 11
+
+
 def _f16_up(v):
     """The smallest fp16 values >= v (v >= 0, float32 array): a scale that a 6-bit code times it must still reach v."""
     h = np.asarray(v, np.float32).astype(np.float16)
