@@ -85,7 +85,7 @@ public sealed unsafe class HipBufferManager : IDisposable
     /// <summary>≙ vkQueueWaitIdle (:334).  Operator calls only enqueue; this waits for the device.</summary>
     public void Synchronize() => Native.Check(Native.nfai_hip_ctx_synchronize(Ctx));
 
-    /// <summary>A weight tensor in its GGUF encoding (fp16 stays fp16; Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 blocks stay quantised) → HBM.</summary>
+    /// <summary>A weight tensor in its GGUF encoding (fp16 stays fp16; IQ4_XS / Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 blocks stay quantised) → HBM.</summary>
     public HipBuffer UploadWeight(GgmlType type, ulong rows, ulong cols, byte[] raw)
     {
         fixed (byte* p = raw)

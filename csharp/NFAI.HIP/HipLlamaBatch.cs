@@ -16,7 +16,7 @@ public sealed unsafe class HipLlamaBatch : IDisposable
     /// K-quant weights (unless quantized), pipeline stages, mixed KV types, separate weights, duplicates.</summary>
     /// quantized: also admits members whose matrices are all Q4_K / Q6_K (Q4_K_M files) through nfai_hip_llama_batch_create_ex with
     /// NFAI_BATCH_QUANT: every quantised row is read and unpacked once per step and multiplied on the matrix cores for all members.
-    /// anyQuant (with quantized): Q5_K, Q8_0, Q4_0 and Q3_K matrices too (Q5_K_M, Q8_0, Q4_0 and Q3_K_S/M files, NFAI_BATCH_QUANT_ANY), in any per-tensor mix.
+    /// anyQuant (with quantized): Q5_K, Q8_0, Q4_0, Q3_K and IQ4_XS matrices too (Q5_K_M, Q8_0, Q4_0, Q3_K_S/M and IQ4_XS files, NFAI_BATCH_QUANT_ANY), in any per-tensor mix.
     /// wide: 1 to 16 whole fp16 models on the fp16-MFMA kernels (nfai_hip_llama_batch_create_wide); every method takes spans of Count.
     public HipLlamaBatch(ReadOnlySpan<ulong> models, uint vocab, bool quantized = false, bool anyQuant = false, bool wide = false)
     {

@@ -12,9 +12,9 @@ public sealed unsafe class HipLlamaWindow : IDisposable
 
     /// <summary>model: a finalized, whole model of the fused path (HipLlamaModel.Handle); maxTokens in [2, 8].  quantized: its matrices
     /// are all Q4_K / Q6_K (Q4_K_M files, NFAI_BATCH_QUANT) instead of all fp16; anyQuant (with quantized): Q5_K,
-    /// Q8_0, Q4_0 and Q3_K matrices too (Q5_K_M, Q8_0, Q4_0 and Q3_K_S/M files, NFAI_BATCH_QUANT_ANY).  The window owns the columns' activation vectors, its
+    /// Q8_0, Q4_0, Q3_K and IQ4_XS matrices too (Q5_K_M, Q8_0, Q4_0, Q3_K_S/M and IQ4_XS files, NFAI_BATCH_QUANT_ANY).  The window owns the columns' activation vectors, its
     /// workspaces and graphs, no weights and no KV cache; the model stays a normal model between window calls.  Throws with tensor and
-    /// type for Q5_K / Q8_0 / Q4_0 / Q3_K weights without anyQuant, pipeline stages, the 1:1 or engine path.</summary>
+    /// type for Q5_K / Q8_0 / Q4_0 / Q3_K / IQ4_XS weights without anyQuant, pipeline stages, the 1:1 or engine path.</summary>
     public HipLlamaWindow(ulong model, uint maxTokens, uint vocab, bool quantized = false, bool anyQuant = false)
     {
         if (anyQuant && !quantized) throw new ArgumentException("anyQuant widens quantized and needs it", nameof(anyQuant));

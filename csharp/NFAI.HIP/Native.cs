@@ -33,7 +33,7 @@ public unsafe struct PpOp
 }
 
 /// <summary>ggml tensor type ids as stored in GGUF (Parser.cs:262-293 names the same ids).</summary>
-public enum GgmlType { F32 = 0, F16 = 1, Q4_0 = 2, Q8_0 = 8, Q3_K = 11, Q4_K = 12, Q5_K = 13, Q6_K = 14 }
+public enum GgmlType { F32 = 0, F16 = 1, Q4_0 = 2, Q8_0 = 8, Q3_K = 11, Q4_K = 12, Q5_K = 13, Q6_K = 14, IQ4_XS = 23 }
 
 [Flags]
 public enum LlamaFlags : uint { None = 0, Unfused = 1, NoGraph = 2, KvF16 = 4, Prefetch = 8, Engine = 16 }

@@ -64,8 +64,12 @@ enum nfai_status {
  * d signed) is accepted under the same shape rules as Q8_0; any other Q4_0 shape is NFAI_ERR_UNSUPPORTED.
  * Q3_K (ggml block_q3_K: hmask[32], qs[64], 12 scale bytes, fp16 d per 256 weights; weight = d * (sc - 32) * (q - 4) with q = two low
  * bits | high bit << 2 and sc a 6-bit scale per 16 weights) is accepted under the same shape rules as Q8_0; any other Q3_K shape is
- * NFAI_ERR_UNSUPPORTED. */
-enum nfai_dtype { NFAI_F32 = 0, NFAI_F16 = 1, NFAI_Q4_0 = 2, NFAI_Q8_0 = 8, NFAI_Q3_K = 11, NFAI_Q4_K = 12, NFAI_Q5_K = 13, NFAI_Q6_K = 14 };
+ * NFAI_ERR_UNSUPPORTED.
+ * IQ4_XS (ggml block_iq4_xs: fp16 d, uint16 scales_h, scales_l[4], qs[128] per 256 weights; weight 32 ib + j = d * (ls - 32) * KV[qs[16 ib + j] & 0xF],
+ * weight 32 ib + 16 + j = d * (ls - 32) * KV[qs[16 ib + j] >> 4] with ls the 6-bit scale of sub-block ib and KV the 16-entry table
+ * {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}) is accepted under the same shape rules as Q8_0; any other
+ * IQ4_XS shape is NFAI_ERR_UNSUPPORTED. */
+enum nfai_dtype { NFAI_F32 = 0, NFAI_F16 = 1, NFAI_Q4_0 = 2, NFAI_Q8_0 = 8, NFAI_Q3_K = 11, NFAI_Q4_K = 12, NFAI_Q5_K = 13, NFAI_Q6_K = 14, NFAI_IQ4_XS = 23 };
 
 const char *nfai_hip_last_error(void);
 int32_t nfai_hip_abi_version(void);
@@ -117,7 +121,7 @@ int32_t nfai_hip_buf_zero(nfai_ctx_t ctx, nfai_buf_t buf);
 int32_t nfai_hip_buf_info(nfai_ctx_t ctx, nfai_buf_t buf, void **device_ptr, uint64_t *bytes);
 /* Weights stay in their native GGUF encoding in HBM (fp16 is NOT widened to fp32 as
  * AbstractComputeCollection.cs:62-77 does; the kernels convert in-register — same operand
- * values).  Validates (type, rows, cols) and uploads rows*row_bytes(type, cols) bytes.  Q8_0: rows*cols/32*34 bytes, Q4_0: rows*cols/32*18 bytes, Q3_K: rows*cols/256*110 bytes, Q5_K:
+ * values).  Validates (type, rows, cols) and uploads rows*row_bytes(type, cols) bytes.  Q8_0: rows*cols/32*34 bytes, Q4_0: rows*cols/32*18 bytes, Q3_K: rows*cols/256*110 bytes, IQ4_XS: rows*cols/256*136 bytes, Q5_K:
  * rows*cols/256*176 bytes, only under their shape rules of enum nfai_dtype (NFAI_ERR_UNSUPPORTED otherwise), repacked at upload for
  * the matrix cores. */
 int32_t nfai_hip_weight_upload(nfai_ctx_t ctx, int32_t ggml_type, uint64_t n_rows, uint64_t n_cols,
@@ -126,7 +130,7 @@ int32_t nfai_hip_weight_bytes(int32_t ggml_type, uint64_t n_rows, uint64_t n_col
 
 /* ---- 1:1 operators: one per ShaderWrapper subclass of the reference.  fp32 activations. ---- */
 /* TokenEmbedShader.Compute (TokenEmbedShader.cs:108-119, GLSL :131-159): y[0:E] = table[tok][0:E];
- * `tok` is a device buffer holding one uint32.  Q8_0 / Q5_K / Q4_0 / Q3_K tables: E %% 256 == 0, uploaded whole with a multiple of 16 rows. */
+ * `tok` is a device buffer holding one uint32.  Q8_0 / Q5_K / Q4_0 / Q3_K / IQ4_XS tables: E %% 256 == 0, uploaded whole with a multiple of 16 rows. */
 int32_t nfai_hip_embed(nfai_ctx_t ctx, nfai_buf_t table, int32_t table_type, nfai_buf_t tok, nfai_buf_t y, uint32_t E);
 /* RMSNormShader.Compute (RMSNormShader.cs:111-122, GLSL :124-151). */
 int32_t nfai_hip_rmsnorm(nfai_ctx_t ctx, nfai_buf_t x, nfai_buf_t gamma, nfai_buf_t y, uint32_t E, float eps);
@@ -189,7 +193,7 @@ int32_t nfai_hip_score_rows(nfai_ctx_t ctx, nfai_buf_t logits, uint32_t T, uint3
 int32_t nfai_hip_attn_decode(nfai_ctx_t ctx, nfai_buf_t q, nfai_buf_t kcache, nfai_buf_t vcache, nfai_buf_t o,
                              uint32_t H, uint32_t Hkv, uint32_t D, uint32_t S, uint32_t C, int32_t kv_type);
 /* [RMSNorm ->] GEMV [-> + residual]: y = res + W * (norm ? rmsnorm(x, gamma) : x).  gamma / res
- * may be 0 (absent).  As every GEMV entry point: Q8_0 / Q5_K / Q4_0 / Q3_K weights under the rules of enum nfai_dtype (K %% 256 == 0, K <= 32768,
+ * may be 0 (absent).  As every GEMV entry point: Q8_0 / Q5_K / Q4_0 / Q3_K / IQ4_XS weights under the rules of enum nfai_dtype (K %% 256 == 0, K <= 32768,
  * a buffer uploaded whole with N %% 16 == 0 rows). */
 /* Batched form of MatrixMultiplyShader (inputRowCount = M > 1, which the reference never uses: MatrixMultiplyShader.cs:31-47
  * takes the row count, TransformerBlock.cs:47-101 always passes 1): C[M][N] fp32 (+ residual R, may be 0) = A[M][K] * W[N][K]^T
@@ -214,14 +218,14 @@ int32_t nfai_hip_attn_prefill(nfai_ctx_t ctx, nfai_buf_t Q_f16, nfai_buf_t K_f16
                               uint32_t Hkv, uint32_t D, uint32_t Spad, uint32_t pos0);
 /* The same batched product with W in Q4_K / Q6_K blocks (a buffer from nfai_hip_weight_upload with N %% 16 == 0 rows): the
  * dequant-in-LDS GEMM — quantised bytes -> registers -> fp16 tile in LDS -> MFMA; the weights are never widened in HBM.
- * Q8_0 / Q5_K / Q4_0 / Q3_K weights: NFAI_ERR_UNSUPPORTED (the model's prefill widens them to fp16 instead). */
+ * Q8_0 / Q5_K / Q4_0 / Q3_K / IQ4_XS weights: NFAI_ERR_UNSUPPORTED (the model's prefill widens them to fp16 instead). */
 int32_t nfai_hip_gemm_kq(nfai_ctx_t ctx, nfai_buf_t A_f16, nfai_buf_t W, int32_t w_type, nfai_buf_t R, nfai_buf_t C, uint32_t M,
                          uint32_t N, uint32_t K);
 int32_t nfai_hip_gemv_fused(nfai_ctx_t ctx, nfai_buf_t W, int32_t w_type, nfai_buf_t x, nfai_buf_t gamma,
                             float eps, nfai_buf_t res, nfai_buf_t y, uint32_t N, uint32_t K);
 /* output RMSNorm (gamma may be 0) -> lm_head GEMV -> SamplingUtils.ArgMax in ONE launch (LlamaModel.cs:123-125, SamplingUtils.cs:43-57):
- * V logits and the first index of their maximum (one uint32 in out_idx).  F16 / F32 tables, and Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 tables with
- * V %% 16 == 0 (Q8_0 / Q5_K / Q4_0 / Q3_K also E %% 256 == 0, E <= 32768). */
+ * V logits and the first index of their maximum (one uint32 in out_idx).  F16 / F32 tables, and IQ4_XS / Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 tables with
+ * V %% 16 == 0 (Q8_0 / Q5_K / Q4_0 / Q3_K / IQ4_XS also E %% 256 == 0, E <= 32768). */
 int32_t nfai_hip_lmhead_argmax(nfai_ctx_t ctx, nfai_buf_t W, int32_t w_type, nfai_buf_t x, nfai_buf_t gamma, float eps,
                                nfai_buf_t logits, nfai_buf_t out_idx, uint32_t V, uint32_t E);
 /* RMSNorm -> Wgate, Wup GEMVs -> SiLU(gate) * up (TransformerBlock.cs:163-171 in one launch). */
@@ -287,7 +291,7 @@ int32_t nfai_hip_llama_destroy(nfai_model_t model);
 /* GGUF tensor by name ("token_embd.weight", "blk.3.attn_q.weight", ..., "output_norm.weight",
  * optional "output.weight"; absent => lm_head tied to token_embd as LlamaModel.cs:64-67).
  * n_rows x n_cols = ggml ne1 x ne0.  Tensors of blocks outside [layer_begin, layer_end) are
- * ignored.  _set_tensor uploads from host; _set_tensor_device adopts bytes already in HBM.  Q8_0 / Q5_K / Q4_0 / Q3_K tensors follow the shape
+ * ignored.  _set_tensor uploads from host; _set_tensor_device adopts bytes already in HBM.  Q8_0 / Q5_K / Q4_0 / Q3_K / IQ4_XS tensors follow the shape
  * rules of enum nfai_dtype and are repacked into an owned copy by both. */
 int32_t nfai_hip_llama_set_tensor(nfai_model_t model, const char *name, int32_t ggml_type,
                                   uint64_t n_rows, uint64_t n_cols, const void *host_bytes);
@@ -352,8 +356,9 @@ int32_t nfai_hip_llama_fetch_tokens(nfai_model_t model, uint32_t n, uint32_t *to
  * K-quant and Q8_0 models: the first call widens every block's matrices to fp16 copies for the MFMA GEMMs (2 bytes per weight,
  * kept until a tensor is replaced) when all of them fit a quarter of the device's memory, else one block's scratch is re-widened
  * per block (NFAI_PREFILL_WIDE_ALL=0 / 1 forces either); the decode path always streams the quantised blocks.  Under
- * NFAI_PREFILL_FUSED=1 Q4_K / Q6_K matrices go through the dequant-in-LDS GEMM, Q8_0, Q5_K, Q4_0 and Q3_K matrices are still widened (a Q4_0
- * weight d * (q - 8) is rounded to fp16 there: |d| * 8 must stay below 65504, as |d| * 127 must for Q8_0). */
+ * NFAI_PREFILL_FUSED=1 Q4_K / Q6_K matrices go through the dequant-in-LDS GEMM, Q8_0, Q5_K, Q4_0, Q3_K and IQ4_XS matrices are still widened (a Q4_0
+ * weight d * (q - 8) is rounded to fp16 there: |d| * 8 must stay below 65504, as |d| * 127 must for Q8_0; a widened IQ4_XS weight is
+ * d * (ls - 32) * KV[q] rounded to fp16: |d| * 32 * 127 must stay below 65504). */
 int32_t nfai_hip_llama_prefill(nfai_model_t model, const uint32_t *tokens, uint32_t n, float *logits_last_host);
 /* The prompt phase of LlamaModel.RunAsync (LlamaModel.cs:103-126 feeds tokenIds one by one and keeps only the LAST token's logits,
  * :128-130): n tokens at positions pos..pos+n-1 leave their K / V rows in the cache, nothing is sampled and no logits are formed
@@ -369,7 +374,7 @@ int32_t nfai_hip_llama_ingest(nfai_model_t model, const uint32_t *tokens, uint32
  * (SamplingUtils.cs:55-56) and logprob_max[i], its log-probability (nfai_hip_score_rows per row).  targets == NULL scores the
  * sequence itself: row i takes tokens[i + 1], the last row no target (logprob[n - 1] = 0); a target NFAI_SCORE_NO_TARGET scores
  * nothing on its row.  Any of the three outputs may be NULL.  Tokens run at positions pos..pos+n-1 and leave their K / V rows.
- * MFMA path (the admission of _prefill, V %% 64 == 0 and an fp16 / Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 head): chunks of max_batch
+ * MFMA path (the admission of _prefill, V %% 64 == 0 and an fp16 / IQ4_XS / Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 head): chunks of max_batch
  * rows through the blocks as _prefill, then per chunk the output norm of all rows and the head as fp16 GEMMs over slabs of 8192
  * vocabulary columns (a quantised head is widened one slab at a time), each folded into the rows' running state: no [n][V] logits
  * and no fp16 copy of the head exist.  The rows' logits come from fp16 operands (normalised row rounded to fp16 x fp16 head,
@@ -457,11 +462,11 @@ int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_t n, nfai
  * admits members whose matrices (token_embd and output included) are all Q4_K or Q6_K in any per-tensor mix, as _set_tensor +
  * _finalize leave them for Q4_K_M files: one step reads every quantised row once, unpacks it once and multiplies it on the matrix
  * cores with the fixed-point activations of all members (kernels_gemv_batch_kqm.hip); a q|k|v whose matrices differ in type runs as
- * two launches.  NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY also admits Q5_K, Q8_0, Q4_0 and Q3_K matrices (Q5_K_M, Q8_0, Q4_0 and Q3_K_S/M files), in any
- * per-tensor mix of the six types; a q|k|v then runs as one launch per type present, three at the most.  NFAI_ERR_INVALID: unknown
+ * two launches.  NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY also admits Q5_K, Q8_0, Q4_0, Q3_K and IQ4_XS matrices (Q5_K_M, Q8_0, Q4_0, Q3_K_S/M and IQ4_XS files), in any
+ * per-tensor mix of the seven types; a q|k|v then runs as one launch per type present, three at the most.  NFAI_ERR_INVALID: unknown
  * flag bits, NFAI_BATCH_QUANT_ANY without NFAI_BATCH_QUANT, and everything _batch_create answers so.  Bit 1 is reserved and stays an
  * unknown bit: flags 2 and 3 have always been answered NFAI_ERR_INVALID, and callers may rely on that answer, so no meaning is given
- * to it.  NFAI_ERR_UNSUPPORTED under the flag(s), naming member, tensor and ggml type: Q5_K / Q8_0 / Q4_0 / Q3_K matrices without
+ * to it.  NFAI_ERR_UNSUPPORTED under the flag(s), naming member, tensor and ggml type: Q5_K / Q8_0 / Q4_0 / Q3_K / IQ4_XS matrices without
  * NFAI_BATCH_QUANT_ANY, fp16 and quantised matrices in one model, a quantised matrix whose row count is not a multiple of 16 (the
  * VALU fallback), a shape the kernels' LDS plan does not hold, and every refusal of _batch_create.
  * The handle works with _batch_step, _batch_step_topk, _batch_greedy, _batch_bytes_per_token (quantised bytes: every T16 plane and norm gain once, an
@@ -469,7 +474,7 @@ int32_t nfai_hip_llama_batch_create(const nfai_model_t *models, uint32_t n, nfai
 enum nfai_batch_flags {
     NFAI_BATCH_QUANT     = 1u << 0,   /* admit members whose matrices are all Q4_K / Q6_K */
     /* 1u << 1 is reserved (see above): it stays an unknown bit */
-    NFAI_BATCH_QUANT_ANY = 1u << 2,   /* with NFAI_BATCH_QUANT: also Q5_K, Q8_0, Q4_0 and Q3_K matrices, any per-tensor mix of the six */
+    NFAI_BATCH_QUANT_ANY = 1u << 2,   /* with NFAI_BATCH_QUANT: also Q5_K, Q8_0, Q4_0, Q3_K and IQ4_XS matrices, any per-tensor mix of the seven */
 };
 int32_t nfai_hip_llama_batch_create_ex(const nfai_model_t *models, uint32_t n, uint32_t flags, nfai_batch_t *out);
 /* ≙ up to 16 LlamaModel instances over one set of weights entering the loop LlamaModel.cs:116-125 together: the wide batch.  Every
@@ -528,10 +533,10 @@ int32_t nfai_hip_llama_batch_profile_step(nfai_batch_t batch, const uint32_t *to
  *      position word, token word and ring. ---- */
 /* ≙ preparing to run up to max_tokens passes of the loop LlamaModel.cs:116-125 of ONE LlamaModel at once.  max_tokens in [2, 8].
  * flags: 0 (all matrices NFAI_F16), NFAI_BATCH_QUANT (all matrices Q4_K / Q6_K) or NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY (all
- * matrices Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0).  The model is admitted as _batch_create /
+ * matrices IQ4_XS / Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0).  The model is admitted as _batch_create /
  * _batch_create_ex admit a member, with the same answers: NFAI_ERR_INVALID for a dead handle, max_tokens outside [2, 8], unknown flag
  * bits, a model not finalized; NFAI_ERR_UNSUPPORTED, naming tensor and ggml type, for a pipeline stage, the 1:1 or engine path,
- * Q5_K / Q8_0 / Q4_0 / Q3_K matrices without NFAI_BATCH_QUANT_ANY, fp16 and quantised matrices in one model, quantised rows % 16 != 0, a shape the kernels' LDS plan does not
+ * Q5_K / Q8_0 / Q4_0 / Q3_K / IQ4_XS matrices without NFAI_BATCH_QUANT_ANY, fp16 and quantised matrices in one model, quantised rows % 16 != 0, a shape the kernels' LDS plan does not
  * hold.  The window owns the columns' activation vectors, workspaces, token / draft / result words, pinned staging and its graphs
  * (one per column count, captured on first use); no weights, no KV cache.  The model stays a normal model: _decode_step, _ingest,
  * _set_pos, _read_kv, _pos between window calls see, and are seen by, the window.  _read: logits are what the model's OWN last token

@@ -11,9 +11,10 @@ OK, ERR_INVALID, ERR_HIP, ERR_OOM, ERR_KV_FULL, ERR_UNSUPPORTED, ERR_STATE = ran
 F32, F16, Q8_0, Q4_K, Q5_K, Q6_K = 0, 1, 8, 12, 13, 14
 Q4_0 = 2
 Q3_K = 11
+IQ4_XS = 23
 BATCH_WIDE_MAX = 16   # NFAI_BATCH_WIDE_MAX: members of nfai_hip_llama_batch_create_wide
 BATCH_QUANT = 1   # nfai_batch_flags: nfai_hip_llama_batch_create_ex admits Q4_K / Q6_K members
-BATCH_QUANT_ANY = 4   # with BATCH_QUANT: Q5_K, Q8_0, Q4_0 and Q3_K matrices too (bit 1 is reserved)
+BATCH_QUANT_ANY = 4   # with BATCH_QUANT: Q5_K, Q8_0, Q4_0, Q3_K and IQ4_XS matrices too (bit 1 is reserved)
 LLAMA_UNFUSED, LLAMA_NO_GRAPH, LLAMA_KV_F16, LLAMA_PREFETCH, LLAMA_ENGINE = 1, 2, 4, 8, 16
 TOKEN_ON_DEVICE = 0xFFFFFFFF
 SCORE_NO_TARGET = 0xFFFFFFFF   # NFAI_SCORE_NO_TARGET: a row of nfai_hip_score_rows / nfai_hip_llama_score without a target

@@ -101,6 +101,8 @@ uint64_t weight_row_bytes(int t, uint64_t n_cols)
         case NFAI_Q4_0_T16: return n_cols % 256 == 0 && n_cols <= 32768 ? n_cols / 32 * GGML_Q4_0_BLOCK : 0;  // (same rules)
         case NFAI_Q3_K:
         case NFAI_Q3_K_T16: return n_cols % 256 == 0 && n_cols <= 32768 ? n_cols / 256 * GGML_Q3_K_BLOCK : 0;  // (same rules)
+        case NFAI_IQ4_XS:
+        case NFAI_IQ4_XS_T16: return n_cols % 256 == 0 && n_cols <= 32768 ? n_cols / 256 * GGML_IQ4_XS_BLOCK : 0;  // (same rules)
         case NFAI_Q5_K:
         case NFAI_Q5_K_T16: return n_cols % 256 == 0 && n_cols <= 32768 ? n_cols / 256 * GGML_Q5_K_BLOCK : 0;  // (same rules)
     }
@@ -515,9 +517,9 @@ NFAI_API int32_t nfai_hip_buf_info(nfai_ctx_t h, nfai_buf_t bh, void **ptr, uint
 NFAI_API int32_t nfai_hip_weight_bytes(int32_t type, uint64_t n_rows, uint64_t n_cols, uint64_t *bytes)
 {
     const uint64_t rb = weight_row_bytes(type, n_cols);
-    if ((type == NFAI_Q8_0 || type == NFAI_Q5_K || type == NFAI_Q4_0 || type == NFAI_Q3_K) && (rb == 0 || n_rows % 16))
+    if ((type == NFAI_Q8_0 || type == NFAI_Q5_K || type == NFAI_Q4_0 || type == NFAI_Q3_K || type == NFAI_IQ4_XS) && (rb == 0 || n_rows % 16))
         return fail(NFAI_ERR_UNSUPPORTED, "weight_bytes: %s needs rows %% 16 == 0, cols %% 256 == 0 and cols <= 32768 (%llu x %llu)",
-                    type == NFAI_Q8_0 ? "Q8_0" : (type == NFAI_Q4_0 ? "Q4_0" : (type == NFAI_Q3_K ? "Q3_K" : "Q5_K")), (unsigned long long)n_rows, (unsigned long long)n_cols);
+                    type == NFAI_Q8_0 ? "Q8_0" : (type == NFAI_Q4_0 ? "Q4_0" : (type == NFAI_Q3_K ? "Q3_K" : (type == NFAI_IQ4_XS ? "IQ4_XS" : "Q5_K"))), (unsigned long long)n_rows, (unsigned long long)n_cols);
     if (rb == 0) return fail(NFAI_ERR_UNSUPPORTED, "weight_bytes: ggml type %d with %llu columns is not supported", type,
                              (unsigned long long)n_cols);
     if (bytes) *bytes = rb * n_rows;
@@ -534,10 +536,10 @@ NFAI_API int32_t nfai_hip_weight_upload(nfai_ctx_t h, int32_t type, uint64_t n_r
     if (rc) return rc;
     const bool t16 = n_rows > 0 && n_rows % 16 == 0;
     const bool q4_t16 = type == NFAI_Q4_K && t16, q6_t16 = type == NFAI_Q6_K && t16, q8_t16 = type == NFAI_Q8_0 && t16;
-    const bool q5_t16 = type == NFAI_Q5_K && t16, q40_t16 = type == NFAI_Q4_0 && t16, q3_t16 = type == NFAI_Q3_K && t16;
-    if (type != NFAI_Q6_K && !q4_t16 && !q8_t16 && !q5_t16 && !q40_t16 && !q3_t16) return nfai_hip_buf_upload(h, *out, 0, host, bytes);
+    const bool q5_t16 = type == NFAI_Q5_K && t16, q40_t16 = type == NFAI_Q4_0 && t16, q3_t16 = type == NFAI_Q3_K && t16, iq4_t16 = type == NFAI_IQ4_XS && t16;
+    if (type != NFAI_Q6_K && !q4_t16 && !q8_t16 && !q5_t16 && !q40_t16 && !q3_t16 && !iq4_t16) return nfai_hip_buf_upload(h, *out, 0, host, bytes);
     // Q6_K: 210-byte native blocks are repacked into the aligned plane layout the kernels read;
-    // Q4_K / Q5_K / Q8_0 / Q4_0 / Q3_K with a multiple of 16 rows (Q5_K / Q8_0 / Q4_0 / Q3_K always: weight_bytes): into the T16 tile layout of kernels_gemv_kqm.hip
+    // Q4_K / Q5_K / Q8_0 / Q4_0 / Q3_K / IQ4_XS with a multiple of 16 rows (Q5_K / Q8_0 / Q4_0 / Q3_K / IQ4_XS always: weight_bytes): into the T16 tile layout of kernels_gemv_kqm.hip
     nfai_buf_t tmp = 0;
     if ((rc = nfai_hip_buf_alloc(h, bytes, &tmp))) return rc;
     if ((rc = nfai_hip_buf_upload(h, tmp, 0, host, bytes))) return rc;
@@ -566,6 +568,10 @@ NFAI_API int32_t nfai_hip_weight_upload(nfai_ctx_t h, int32_t type, uint64_t n_r
     } else if (q3_t16) {
         e = launch_repack_q3k_t16(buf_of(tmp)->ptr, buf_of(*out)->ptr, n_rows, n_cols, c->stream);
         buf_of(*out)->w_layout = NFAI_Q3_K_T16;
+        buf_of(*out)->w_rows = n_rows;
+    } else if (iq4_t16) {
+        e = launch_repack_iq4xs_t16(buf_of(tmp)->ptr, buf_of(*out)->ptr, n_rows, n_cols, c->stream);
+        buf_of(*out)->w_layout = NFAI_IQ4_XS_T16;
         buf_of(*out)->w_rows = n_rows;
     } else {
         e = launch_repack_q6k(buf_of(tmp)->ptr, buf_of(*out)->ptr, n_rows * n_cols / 256, c->stream);
@@ -601,9 +607,9 @@ NFAI_API int32_t nfai_hip_embed(nfai_ctx_t h, nfai_buf_t table, int32_t type, nf
     BUF_OR_FAIL(by, y);
     NEED(bk, 1, 4);
     NEED(by, E, 4);
-    if (type == NFAI_Q4_K || type == NFAI_Q6_K || type == NFAI_Q8_0 || type == NFAI_Q5_K || type == NFAI_Q4_0 || type == NFAI_Q3_K) {
+    if (type == NFAI_Q4_K || type == NFAI_Q6_K || type == NFAI_Q8_0 || type == NFAI_Q5_K || type == NFAI_Q4_0 || type == NFAI_Q3_K || type == NFAI_IQ4_XS) {
         const uint64_t rb = weight_row_bytes(type, E);
-        if (rb == 0) return fail(NFAI_ERR_UNSUPPORTED, "embed: K-quant / Q8_0 / Q4_0 table needs E %% 256 == 0 (Q3_K / Q5_K / Q8_0 / Q4_0: E <= 32768) (E=%u)", E);
+        if (rb == 0) return fail(NFAI_ERR_UNSUPPORTED, "embed: K-quant / Q8_0 / Q4_0 table needs E %% 256 == 0 (IQ4_XS / Q3_K / Q5_K / Q8_0 / Q4_0: E <= 32768) (E=%u)", E);
         int lt;
         { int rc = resolve_layout(__func__, bt, type, bt->bytes / rb, &lt); if (rc) return rc; }
         LAUNCH_TRY(launch_embed_kq(bt->ptr, lt, bt->bytes / rb, static_cast<const uint32_t *>(bk->ptr), static_cast<float *>(by->ptr), E, c->stream));
@@ -1028,8 +1034,8 @@ NFAI_API int32_t nfai_hip_gemm_kq(nfai_ctx_t h, nfai_buf_t A, nfai_buf_t W, int3
     if (M == 0 || N % 64 || K % 256 || K == 0) return fail(NFAI_ERR_INVALID, "gemm_kq: needs M > 0, N %% 64 == 0, K %% 256 == 0 (M=%u N=%u K=%u)", M, N, K);
     int lt;
     { int rc = resolve_layout(__func__, bw, type, N, &lt); if (rc) return rc; }
-    if (lt != NFAI_Q4_K_T16 && lt != NFAI_Q6_K_T16)  // Q8_0 / Q5_K / Q4_0 / Q3_K: no dequant-in-LDS form; the model widens them to fp16 instead
-        return fail(NFAI_ERR_UNSUPPORTED, "gemm_kq: W must be a Q4_K / Q6_K buffer uploaded whole with a multiple of 16 rows (Q5_K, Q8_0, Q4_0 and Q3_K are not supported)");
+    if (lt != NFAI_Q4_K_T16 && lt != NFAI_Q6_K_T16)  // Q8_0 / Q5_K / Q4_0 / Q3_K / IQ4_XS: no dequant-in-LDS form; the model widens them to fp16 instead
+        return fail(NFAI_ERR_UNSUPPORTED, "gemm_kq: W must be a Q4_K / Q6_K buffer uploaded whole with a multiple of 16 rows (Q5_K, Q8_0, Q4_0, Q3_K and IQ4_XS are not supported)");
     NEED(ba, (uint64_t)M * K, 2);
     NEED(bc, (uint64_t)M * N, 4);
     if (br) NEED(br, (uint64_t)M * N, 4);

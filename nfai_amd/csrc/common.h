@@ -118,7 +118,7 @@ struct GemvArgs {
     // other blocks' launches and advances the hand-off epoch; this launch's own RoPE forms cos/sin itself
     struct Begin {
         bool on = false;
-        const void *emb = nullptr;   // [emb_rows][K]: F16 / F32 row-major, or the T16 layout of a Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 table
+        const void *emb = nullptr;   // [emb_rows][K]: F16 / F32 row-major, or the T16 layout of an IQ4_XS / Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 table
         int emb_type = NFAI_F16;
         uint64_t emb_rows = 0;
         const uint32_t *tok = nullptr;
@@ -140,21 +140,22 @@ enum GemvMode { GEMV_PLAIN = 0, GEMV_RESIDUAL = 1, GEMV_QKV_ROPE = 2, GEMV_GATEU
 
 // Internal weight-type codes of the T16 layouts (t16.h): same bytes as the ggml type, rows
 // grouped in tiles of 16.  Never seen across the C ABI: uploads with rows % 16 == 0 are repacked into them.
-// Q8_0, Q5_K, Q4_0 and Q3_K exist only in the T16 layout (rows % 16 == 0 is a rule of their upload); is_kquant covers them (block-quantised,
+// Q8_0, Q5_K, Q4_0, Q3_K and IQ4_XS exist only in the T16 layout (rows % 16 == 0 is a rule of their upload); is_kquant covers them (block-quantised,
 // same paths).
-constexpr int NFAI_Q4_0_T16 = 102, NFAI_Q8_0_T16 = 108, NFAI_Q3_K_T16 = 111, NFAI_Q4_K_T16 = 112, NFAI_Q5_K_T16 = 113, NFAI_Q6_K_T16 = 114;
+constexpr int NFAI_Q4_0_T16 = 102, NFAI_Q8_0_T16 = 108, NFAI_Q3_K_T16 = 111, NFAI_Q4_K_T16 = 112, NFAI_Q5_K_T16 = 113, NFAI_Q6_K_T16 = 114, NFAI_IQ4_XS_T16 = 123;
 constexpr int NFAI_KQ_MIXED = 115;   // GemvArgs::w_type of a q|k|v launch whose segments are Q4_K_T16 / Q6_K_T16 per seg6_mask
 constexpr int NFAI_KQ_MIXED5 = 116;  // the same with Q5_K_T16 / Q6_K_T16 segments (Q5_K_M files)
 inline bool is_kquant(int t)
 {
     return t == NFAI_Q4_K || t == NFAI_Q6_K || t == NFAI_Q4_K_T16 || t == NFAI_Q6_K_T16 || t == NFAI_Q8_0 || t == NFAI_Q8_0_T16 ||
-           t == NFAI_Q5_K || t == NFAI_Q5_K_T16 || t == NFAI_Q4_0 || t == NFAI_Q4_0_T16 || t == NFAI_Q3_K || t == NFAI_Q3_K_T16;
+           t == NFAI_Q5_K || t == NFAI_Q5_K_T16 || t == NFAI_Q4_0 || t == NFAI_Q4_0_T16 || t == NFAI_Q3_K || t == NFAI_Q3_K_T16 ||
+           t == NFAI_IQ4_XS || t == NFAI_IQ4_XS_T16;
 }
-inline bool is_t16(int t) { return t == NFAI_Q4_K_T16 || t == NFAI_Q6_K_T16 || t == NFAI_Q8_0_T16 || t == NFAI_Q5_K_T16 || t == NFAI_Q4_0_T16 || t == NFAI_Q3_K_T16; }
+inline bool is_t16(int t) { return t == NFAI_Q4_K_T16 || t == NFAI_Q6_K_T16 || t == NFAI_Q8_0_T16 || t == NFAI_Q5_K_T16 || t == NFAI_Q4_0_T16 || t == NFAI_Q3_K_T16 || t == NFAI_IQ4_XS_T16; }
 inline int ggml_type_of(int t)
 {
     return t == NFAI_Q4_K_T16 ? NFAI_Q4_K
-                              : (t == NFAI_Q6_K_T16 ? NFAI_Q6_K : (t == NFAI_Q8_0_T16 ? NFAI_Q8_0 : (t == NFAI_Q5_K_T16 ? NFAI_Q5_K : (t == NFAI_Q4_0_T16 ? NFAI_Q4_0 : (t == NFAI_Q3_K_T16 ? NFAI_Q3_K : t)))));
+                              : (t == NFAI_Q6_K_T16 ? NFAI_Q6_K : (t == NFAI_Q8_0_T16 ? NFAI_Q8_0 : (t == NFAI_Q5_K_T16 ? NFAI_Q5_K : (t == NFAI_Q4_0_T16 ? NFAI_Q4_0 : (t == NFAI_Q3_K_T16 ? NFAI_Q3_K : (t == NFAI_IQ4_XS_T16 ? NFAI_IQ4_XS : t))))));
 }
 
 hipError_t launch_gemv(const GemvArgs &a, hipStream_t s);     // any weight type; K-quants go to launch_gemv_kq / _kqm
@@ -188,6 +189,7 @@ hipError_t launch_repack_q80_t16(const void *native, void *tiled, uint64_t rows,
 hipError_t launch_repack_q5k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
 hipError_t launch_repack_q40_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
 hipError_t launch_repack_q3k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
+hipError_t launch_repack_iq4xs_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s);
 hipError_t launch_embed_kqt(const void *table, int type, uint64_t n_rows, const uint32_t *tok, float *y, uint32_t E, hipStream_t s);
 hipError_t launch_embed_rows_kqt(const void *table, int type, uint64_t n_rows, const uint32_t *toks, float *y, uint32_t T, uint32_t E, hipStream_t s);
 hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64_t cols, void *out_f16, hipStream_t s);  // T16 K-quant / Q8_0 -> fp16 [rows][cols]
@@ -369,7 +371,7 @@ size_t window_attn_bytes(uint32_t H, uint32_t D);
 hipError_t launch_window_attn(const WindowAttnArgs &a, hipStream_t s);
 // x[b] = row tok[b] of the fp16 embedding table, widened (TokenEmbedShader.cs:131-159), b < n
 hipError_t launch_batch_embed(const void *table, uint64_t n_rows, uint32_t E, const uint32_t *tok, float *const *x, uint32_t n, hipStream_t s);
-// The same launches on Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 matrices in the T16 layout (kernels_gemv_batch_kqm.hip): W[i] are T16 tensors of ONE
+// The same launches on IQ4_XS / Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 matrices in the T16 layout (kernels_gemv_batch_kqm.hip): W[i] are T16 tensors of ONE
 // type (a q|k|v of mixed types is split by type into up to three launches), seg_role[i] says which of q (0), k (1), v (2) segment i of a q|k|v launch is.
 struct BatchKqArgs : BatchGemvArgs {
     int w_type = 0;                    // a T16 type (is_t16)

@@ -1,4 +1,4 @@
-// kernels_gemv_batch_kqm.hip — the batched decode step (kernels_gemv_batch.hip) on Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 weights in the T16 layout: every
+// kernels_gemv_batch_kqm.hip — the batched decode step (kernels_gemv_batch.hip) on IQ4_XS / Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 weights in the T16 layout: every
 // quantised weight row is read from HBM ONCE, unpacked ONCE and multiplied on the matrix cores with the fixed-point activations of up to
 // 8 sequences (MatrixMultiplyShader.cs:255-289 at M = B on weights the reference cannot load, Parser.cs:111-114; the prologues and
 // epilogues of TransformerBlock.Compute, TransformerBlock.cs:127-184, per column as in k_bgemv).  A separate family: k_gemv_kqt and
@@ -10,9 +10,9 @@
 //             tile has NBT <= 16 super-blocks ("slots"); wave w owns slots w * BPW .. + BPW - 1 (BPW = 2 when NBT > 8: at most 8 waves, so
 //             that a wave may use 256 VGPRs) and stages exactly those super-blocks of every column (kqm_stage: 2^S, three base-256
 //             digits as A fragments, scale-group sums): nothing staged is read by another wave, and a K tile needs no barrier.
-//   step      one super-block of one 16-row tile: 1760 B (Q3_K) / 2304 B (Q4_K, Q4_0) / 2816 B (Q5_K) / 3360 B (Q6_K) / 4352 B (Q8_0) per wave, two steps
+//   step      one super-block of one 16-row tile: 1760 B (Q3_K) / 2176 B (IQ4_XS) / 2304 B (Q4_K, Q4_0) / 2816 B (Q5_K) / 3360 B (Q6_K) / 4352 B (Q8_0) per wave, two steps
 //             (B = 8; Q5_K, Q6_K and Q8_0 at B = 4) or four in flight.  The loads, the nibble / fifth-bit / 6-bit unpack and the
-//             header decode (get_scale_min_k4, the int8 scales, the fp16 d of Q8_0 / Q4_0) happen once (kqm_unpack); then per column,
+//             header decode (get_scale_min_k4, the int8 scales, the fp16 d of Q8_0 / Q4_0, the codebook lookup and the 6-bit scales of IQ4_XS) happen once (kqm_unpack); then per column,
 //             in branch-free groups of up to four: four A fragments + the sums + S from LDS, four v_mfma_i32_16x16x64_i8 against the unpacked B
 //             operand held in registers, the fp32 scale epilogue, ldexpf by the column's exponent, one add into the column's sum.
 //   LDS       1 KiB of fragments + 64 B of sums + 4 B of S per super-block and column.  A K tile is at most 16 super-blocks (4096
@@ -23,7 +23,8 @@
 //             next tile's x is requested while the current one is multiplied.
 //   mixed     a q|k|v whose segments differ in type is split by type into up to three launches (llama_batch.hip), so a launch stages
 //             one fragment layout only: Q4_K's (Q5_K stages as Q4_K: same sub-blocks, scales and mins; Q4_0 stages as Q4_K too: its
-//             32-blocks are the sub-blocks, d the scale and 8 d the min, t16.h), Q6_K's (Q3_K stages as Q6_K: same 16-weight groups,
+//             32-blocks are the sub-blocks, d the scale and 8 d the min, t16.h; IQ4_XS likewise: its operand bytes are the table values of its codes,
+//             d * (ls - 32) the scale and the min 0, kqm.h), Q6_K's (Q3_K stages as Q6_K: same 16-weight groups,
 //             its bytes biased by 28 so that Q6_K's -32 leaves q - 4, kqm.h) or Q8_0's.
 //   order     a (row, column) sum: lane (G, r) adds its 64-weight partials of slot s of the K tiles in tile order; the four G meet by
 //             rows4_sum; the slots are added in slot order in four interleaved chains.  Slots and tiles depend on K only (not on the
@@ -94,8 +95,9 @@ template <int QT, int B, int MODE, bool NORM, int BPW>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_bgemv_kq(const BKqParams p)
 {
     constexpr bool IS6 = QT == NFAI_Q6_K_T16, IS5 = QT == NFAI_Q5_K_T16, IS8 = QT == NFAI_Q8_0_T16, IS40 = QT == NFAI_Q4_0_T16, IS3 = QT == NFAI_Q3_K_T16;
-    static_assert(IS6 || IS5 || IS8 || IS40 || IS3 || QT == NFAI_Q4_K_T16, "Q3_K, Q4_0, Q4_K, Q5_K, Q6_K or Q8_0 in the T16 layout");
-    using Regs = typename std::conditional<IS6, Q6T, typename std::conditional<IS5, Q5T, typename std::conditional<IS8, Q8T, typename std::conditional<IS40, Q40T, typename std::conditional<IS3, Q3T, Q4T>::type>::type>::type>::type>::type;
+    constexpr bool ISI4 = QT == NFAI_IQ4_XS_T16;
+    static_assert(IS6 || IS5 || IS8 || IS40 || IS3 || ISI4 || QT == NFAI_Q4_K_T16, "IQ4_XS, Q3_K, Q4_0, Q4_K, Q5_K, Q6_K or Q8_0 in the T16 layout");
+    using Regs = typename std::conditional<IS6, Q6T, typename std::conditional<IS5, Q5T, typename std::conditional<IS8, Q8T, typename std::conditional<IS40, Q40T, typename std::conditional<IS3, Q3T, typename std::conditional<ISI4, IQ4T, Q4T>::type>::type>::type>::type>::type>::type;
     constexpr int R = MODE == GEMV_GATEUP ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x, lane = tid & 63, nw = blockDim.x >> 6;
@@ -177,7 +179,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 }
                 uint8_t *xb = xa + (size_t)b * NBT * 1024;
                 float *sb = sums + b * NBT * 16;
-                kqm_stage<!IS6 && !IS8 && !IS3, IS6 || IS3, IS8>(v, slot, lane, xb, xb, sb, sb, sexp + b * NBT);   // (Q5_K and Q4_0 stage as Q4_K, Q3_K as Q6_K)
+                kqm_stage<!IS6 && !IS8 && !IS3, IS6 || IS3, IS8>(v, slot, lane, xb, xb, sb, sb, sexp + b * NBT);   // (Q5_K, Q4_0 and IQ4_XS stage as Q4_K, Q3_K as Q6_K)
             }
         }
     };
@@ -194,6 +196,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             else if constexpr (IS8) buf = q8t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
             else if constexpr (IS40) buf = q40t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
             else if constexpr (IS3) buf = q3t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
+            else if constexpr (ISI4) buf = iq4t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
             else buf = q4t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
             ++ist;
             if (++i_i == (uint32_t)BPW) { i_i = 0; if (++i_t == (uint32_t)R) { i_t = 0; if (++i_ui == nunits) { i_ui = 0; ++i_tile; } } }
@@ -204,7 +207,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if constexpr (BPW == 2) load_x(0, std::integral_constant<int, 1>{});
     __builtin_amdgcn_sched_barrier(0);
     // steps in flight per wave (the depth changes no result): four where the registers allow (18 per Q8_0 step, 17 per Q6_K step, 14
-    // per Q5_K step, 12 per Q4_K step, 10 per Q3_K step, 9 per Q4_0 step).  Q8_0 takes Q6_K's depth and column groups: what compiles without scratch, not measured
+    // per Q5_K step, 12 per Q4_K step, 10 per Q3_K or IQ4_XS step, 9 per Q4_0 step).  Q8_0 takes Q6_K's depth and column groups: what compiles without scratch, not measured
     // against deeper buffering.
     constexpr bool WIDE = IS6 || IS8;
     constexpr int NBUF = (B == 8 || ((WIDE || IS5) && B == 4)) ? 2 : 4;
@@ -559,6 +562,7 @@ hipError_t launch_batch_gemv_kq(const BatchKqArgs &a, hipStream_t s)
     if (a.w_type == NFAI_Q8_0_T16) return dispatch_bkq_b<NFAI_Q8_0_T16>(p, pl, a.mode, norm, s);
     if (a.w_type == NFAI_Q4_0_T16) return dispatch_bkq_b<NFAI_Q4_0_T16>(p, pl, a.mode, norm, s);
     if (a.w_type == NFAI_Q3_K_T16) return dispatch_bkq_b<NFAI_Q3_K_T16>(p, pl, a.mode, norm, s);
+    if (a.w_type == NFAI_IQ4_XS_T16) return dispatch_bkq_b<NFAI_IQ4_XS_T16>(p, pl, a.mode, norm, s);
     return dispatch_bkq_b<NFAI_Q4_K_T16>(p, pl, a.mode, norm, s);
 }
 

@@ -17,7 +17,7 @@
 // signed base-256 digits; sum q * x' = S0 + 256 S1 + 65536 S2 is exact in int32, the K-quant scales
 // (d * sc, dmin * m, the -32 offset of Q6_K via the group sums of x') are applied in fp32 exactly
 // as ggml defines the block; Q8_0 (d * q, q a signed byte) needs neither sums nor offsets: one d per lane
-// and MFMA; Q4_0 (d * (q - 8), q a nibble) takes Q4_K's staging and sums of x' with d and 8 d in place of the scale and the min; Q3_K (d * (sc - 32) * (q - 4), q three bits) takes Q6_K's staging, its -4 through the per-16 sums of x' as Q6_K's -32.  The only approximation is x' = round(x * 2^S): 24 bits relative to
+// and MFMA; Q4_0 (d * (q - 8), q a nibble) takes Q4_K's staging and sums of x' with d and 8 d in place of the scale and the min; Q3_K (d * (sc - 32) * (q - 4), q three bits) takes Q6_K's staging, its -4 through the per-16 sums of x' as Q6_K's -32; IQ4_XS (d * (ls - 32) * KV[q], q a nibble that indexes a 16-entry table of signed bytes) takes Q4_K's staging and Q4_0's four MFMAs on the table values, looked up in registers (iq4_lut4, t16.h), and like Q8_0 needs no sums.  The only approximation is x' = round(x * 2^S): 24 bits relative to
 // the largest |x| of the super-block.  Against the fp32 oracle the differences are at the level of
 // fp32 summation-order noise (tests/test_gpu_kquant.py states the tolerance; max |dlogit| 1.5e-5 at 3B).
 //
@@ -129,12 +129,14 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
     // QT = NFAI_Q5_K_T16: the Q4_K staging (fragments and sums of x'); NFAI_KQ_MIXED5: Q5_K and Q6_K segments as NFAI_KQ_MIXED.
     // QT = NFAI_Q4_0_T16: the Q4_K staging too (t16.h); launched on Q4_0 segments only (llama.hip gives them their own launch).
     // QT = NFAI_Q3_K_T16: the Q6_K staging (fragments and per-16 sums of x', t16.h); launched on Q3_K segments only, as Q4_0.
+    // QT = NFAI_IQ4_XS_T16: the Q4_K staging (its sums of x' go unread); launched on IQ4_XS segments only, as Q4_0.
     constexpr bool HAS8 = QT == NFAI_Q8_0_T16, HAS5 = QT == NFAI_Q5_K_T16 || QT == NFAI_KQ_MIXED5, IS40 = QT == NFAI_Q4_0_T16, IS3 = QT == NFAI_Q3_K_T16;
-    constexpr bool HAS4 = !HAS8 && !IS3 && QT != NFAI_Q6_K_T16, HAS6 = !HAS8 && !IS40 && QT != NFAI_Q4_K_T16 && QT != NFAI_Q5_K_T16, MIXED = HAS4 && HAS6;
+    constexpr bool ISI4 = QT == NFAI_IQ4_XS_T16;
+    constexpr bool HAS4 = !HAS8 && !IS3 && QT != NFAI_Q6_K_T16, HAS6 = !HAS8 && !IS40 && !ISI4 && QT != NFAI_Q4_K_T16 && QT != NFAI_Q5_K_T16, MIXED = HAS4 && HAS6;
     static_assert(!MIXED || MODE == GEMV_QKV_ROPE, "mixed encodings exist for the q|k|v launch only");
     using Regs = typename std::conditional<
         QT == NFAI_Q4_K_T16, Q4T,
-        typename std::conditional<HAS8, Q8T, typename std::conditional<QT == NFAI_Q5_K_T16, Q5T, typename std::conditional<IS40, Q40T, typename std::conditional<IS3, Q3T, Q6T>::type>::type>::type>::type>::type;
+        typename std::conditional<HAS8, Q8T, typename std::conditional<QT == NFAI_Q5_K_T16, Q5T, typename std::conditional<IS40, Q40T, typename std::conditional<IS3, Q3T, typename std::conditional<ISI4, IQ4T, Q6T>::type>::type>::type>::type>::type>::type;
     constexpr int R = MODE == GEMV_GATEUP ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x, lane = tid & 63, nw = blockDim.x >> 6;
@@ -206,6 +208,8 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
             buf = q40t_load(p, seg, tile, blk, lane);
         } else if constexpr (IS3) {
             buf = q3t_load(p, seg, tile, blk, lane);
+        } else if constexpr (ISI4) {
+            buf = iq4t_load(p, seg, tile, blk, lane);
         } else {
             if ((p.seg6 >> seg) & 1u) {
                 buf = q6t_load(p, seg, tile, blk, lane);
@@ -302,6 +306,7 @@ __global__ __launch_bounds__(1024) void k_gemv_kqt(const KqmParams p)
                     if constexpr (QT == NFAI_Q4_K_T16) a = q4t_dot(buf, af, f32x2{sm[0], sm[1]}, g);
                     else if constexpr (QT == NFAI_Q5_K_T16) a = q5t_dot(buf, af, f32x2{sm[0], sm[1]}, g);
                     else if constexpr (IS40) a = q40t_dot(buf, af, f32x2{sm[0], sm[1]});
+                    else if constexpr (ISI4) a = iq4t_dot(buf, af, g);
                     else if constexpr (HAS5) a = q5t_dot(Q5T{buf.qla, buf.qlb, buf.sc, u32x2{buf.qh[0], buf.qh[1]}}, af, f32x2{sm[0], sm[1]}, g);
                     else a = q4t_dot(Q4T{buf.qla, buf.qlb, buf.sc}, af, f32x2{sm[0], sm[1]}, g);
                 }
@@ -493,6 +498,21 @@ __global__ void k_repack_q40_t16(const uint8_t *src, uint8_t *dst, uint32_t n_ti
     }
 }
 
+// ---- IQ4_XS repack: native 136-byte blocks (row-major: d, scales_h, scales_l[4], qs[128]) -> T16 planes (same bytes) -----------------
+// Plane 0: qs[16 (2G + h) .. + 16) of the row's block to lane (G, r) of half h (Q4_0's plane); plane 1: the block's first 8 bytes.
+__global__ void k_repack_iq4xs_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
+{
+    const uint64_t tb = blockIdx.x;
+    const uint32_t tile = (uint32_t)(tb / NB), blk = (uint32_t)(tb % NB), t = threadIdx.x;
+    const uint64_t nblk = t16_nblk(n_tiles, NB);
+    // native blocks are 8-byte aligned within a row of an aligned buffer, but a caller's device pointer need not be: byte copies
+    for (uint32_t e = t; e < 2048; e += blockDim.x) {
+        const uint32_t h = e >> 10, ln = (e >> 4) & 63, b = e & 15, G = ln >> 4, r = ln & 15;
+        t16_iq4_qs(dst, tb)[e] = src[((uint64_t)(tile * 16 + r) * NB + blk) * GGML_IQ4_XS_BLOCK + 8 + 16 * (2 * G + h) + b];
+    }
+    if (t < 128) t16_iq4_hdr(dst, nblk, tb)[t] = src[((uint64_t)(tile * 16 + (t >> 3)) * NB + blk) * GGML_IQ4_XS_BLOCK + (t & 7)];
+}
+
 // ---- Q3_K repack: native 110-byte blocks (row-major: hmask[32], qs[64], scales[12], d) -> T16 planes (same bytes) --------------------
 // Plane 0: the lane's 16 qs bytes as they are; plane 1: the bit order of t16.h; planes 2 and 3: the scale bytes and d as they are.
 __global__ void k_repack_q3k_t16(const uint8_t *src, uint8_t *dst, uint32_t n_tiles, uint32_t NB)
@@ -569,6 +589,10 @@ hipError_t launch_repack_q40_t16(const void *native, void *tiled, uint64_t rows,
 hipError_t launch_repack_q3k_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
 {
     return launch_repack_t16(k_repack_q3k_t16, 256, native, tiled, rows, cols, s);
+}
+hipError_t launch_repack_iq4xs_t16(const void *native, void *tiled, uint64_t rows, uint64_t cols, hipStream_t s)
+{
+    return launch_repack_t16(k_repack_iq4xs_t16, 256, native, tiled, rows, cols, s);
 }
 
 // ---- rows of a T16 table -> fp32 (embedding gather): row tok[t] to y + t * E (prefill, single token) or, y == nullptr, to x[t] (the
@@ -684,6 +708,25 @@ __global__ __launch_bounds__(256) void k_dequant_t16(const uint8_t *W, _Float16 
                 *reinterpret_cast<f16x8 *>(orow + (2 * g + h) * 32 + c * 8) = o;
             }
         }
+    } else if constexpr (QT == NFAI_IQ4_XS_T16) {
+        const u32x2 hdr = *reinterpret_cast<const u32x2 *>(t16_iq4_hdr(W, nblk, tb) + r * 8);
+        const float d = h2f_lo(hdr[0]);
+#pragma unroll
+        for (int h = 0; h < 2; h++) {  // sub-block 2g + h of row r: weights 0..15 = the table values of the low nibbles, 16..31 = of the high nibbles
+            const u32x4 q = load_nt16(t16_iq4_qs(W, tb) + h * 1024 + lane * 16);
+            const float dl = d * (float)(iq4xs_scale(hdr[0], hdr[1], 2 * g + h) - 32);  // (d * (ls - 32)) * KV[q], as the format writes it
+#pragma unroll
+            for (int c = 0; c < 4; c++) {  // 8 weights: nibble c >> 1 of bytes 8 (c & 1) .. + 8
+                f16x8 o;
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    const uint32_t qw = q[2 * (c & 1) + i], v4 = iq4_lut4((c >> 1) ? (qw >> 4) : qw);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) o[4 * i + e] = f16_of_f32(dl * (float)(int8_t)((v4 >> (8 * e)) & 0xFFu));
+                }
+                *reinterpret_cast<f16x8 *>(orow + (2 * g + h) * 32 + c * 8) = o;
+            }
+        }
     } else if constexpr (QT == NFAI_Q3_K_T16) {
         const u32x4 q = load_nt16(t16_q3k_qs(W, tb) + lane * 16);
         const u32x2 hm = *reinterpret_cast<const u32x2 *>(t16_q3k_hm(W, nblk, tb) + lane * 8);
@@ -770,6 +813,7 @@ hipError_t launch_dequant_t16_f16(const void *W, int type, uint64_t rows, uint64
     else if (type == NFAI_Q5_K_T16) NFAI_DQ(NFAI_Q5_K_T16);
     else if (type == NFAI_Q4_0_T16) NFAI_DQ(NFAI_Q4_0_T16);
     else if (type == NFAI_Q3_K_T16) NFAI_DQ(NFAI_Q3_K_T16);
+    else if (type == NFAI_IQ4_XS_T16) NFAI_DQ(NFAI_IQ4_XS_T16);
     else if (type == NFAI_Q8_0_T16) NFAI_DQ(NFAI_Q8_0_T16);
     else return hipErrorInvalidValue;
 #undef NFAI_DQ
@@ -927,6 +971,7 @@ hipError_t launch_gemv_kqm(const GemvArgs &a, hipStream_t s)
     if (a.w_type == NFAI_Q8_0_T16) return q4t_mode<NFAI_Q8_0_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     if (a.w_type == NFAI_Q4_0_T16) return q4t_mode<NFAI_Q4_0_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     if (a.w_type == NFAI_Q3_K_T16) return q4t_mode<NFAI_Q3_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
+    if (a.w_type == NFAI_IQ4_XS_T16) return q4t_mode<NFAI_IQ4_XS_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     if (a.w_type == NFAI_Q4_K_T16) return q4t_mode<NFAI_Q4_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
     return q4t_mode<NFAI_Q6_K_T16>(p, a.mode, bpw, grid, nw * 64, lds, s);
 }

@@ -45,6 +45,7 @@ struct Q5T { u32x4 q0, q1, hdr; u32x2 qh; };
 struct Q6T { u32x4 qla, qlb, qh, sc; uint32_t d; };
 struct Q40T { u32x4 q0, q1; uint32_t d; };
 struct Q3T { u32x4 q; u32x2 h; uint32_t s0, s1, s2, d; };
+struct IQ4T { u32x4 q0, q1; u32x2 hdr; };
 
 __device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t mask, uint32_t bits) { return (a & mask) | bits; }
 
@@ -345,8 +346,64 @@ __device__ __forceinline__ float q3t_dot(const Q3T &w, const i32x4 (&af)[4], f32
     return d * tot;
 }
 
+// One step of a wave on an IQ4_XS T16 tensor: the codes (2 x 1 KiB: q{h} = the 16 qs bytes of the lane's sub-block 2G + h, Q4_0's plane)
+// and the 8-byte headers of the 16 rows (128 B): d | scales_h in hdr[0], scales_l[4] in hdr[1].  2176 bytes, 10 VGPRs per step.
+__device__ __forceinline__ IQ4T iq4t_load_raw(const uint8_t *base, uint64_t n_tiles, uint32_t NB, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    const uint64_t tb = t16_tb(tile, NB, blk), nblk = t16_nblk(n_tiles, NB);
+    IQ4T r;
+    r.q0 = load_nt16(t16_iq4_qs(base, tb) + lane * 16);
+    r.q1 = load_nt16(t16_iq4_qs(base, tb) + 1024 + lane * 16);
+    r.hdr = __builtin_nontemporal_load((const GLOBAL_AS u32x2 *)(t16_iq4_hdr(base, nblk, tb) + (lane & 15) * 8));
+    return r;
+}
+
+__device__ __forceinline__ IQ4T iq4t_load(const KqmParams &p, uint32_t seg, uint32_t tile, uint32_t blk, uint32_t lane)
+{
+    return iq4t_load_raw(p.W[seg], p.seg_tiles[seg], p.NB, tile, blk, lane);
+}
+
+// The B operand of the low (HI = false) or high nibbles of 16 code bytes: one signed table byte per weight (iq4_lut4: the codebook
+// lookup in registers, 7 VALU operations per dword of low nibbles, 8 of high ones (one more shift): 120 per step, where Q4_0's
+// nibble masks take 24).
+template <bool HI>
+__device__ __forceinline__ i32x4 iq4t_operand(const u32x4 q)
+{
+    u32x4 b;
+#pragma unroll
+    for (int i = 0; i < 4; i++) b[i] = iq4_lut4(HI ? q[i] >> 4 : q[i]);
+    return __builtin_bit_cast(i32x4, b);
+}
+
+// The fp32 scales d * (ls - 32) of the lane's sub-blocks 2G and 2G+1 (the product rounded to fp32, as the format writes dl).
+__device__ __forceinline__ void iq4t_scales(const IQ4T &w, uint32_t g, float &da, float &db)
+{
+    const float d = h2f_lo(w.hdr[0]);
+    da = d * (float)(iq4xs_scale(w.hdr[0], w.hdr[1], 2 * g) - 32);
+    db = d * (float)(iq4xs_scale(w.hdr[0], w.hdr[1], 2 * g + 1) - 32);
+}
+
+// 64 weights of one lane (sub-blocks 2G: q0, 2G+1: q1) against the activations staged as for Q4_K: Q4_0's four MFMAs (the low nibbles
+// of q{h} are weights 0..15 of sub-block 2G + h, A-fragment slot 2h, the high nibbles weights 16..31, slot 2h + 1; both halves of a
+// sub-block accumulate into ONE int32 accumulator) on the table values of the codes: signed bytes -127 .. 113, as Q8_0's operands
+// are (32 x 127 x 128 per accumulator at the most).  No offset and no min, so no term in the sums of x'.
+__device__ __forceinline__ float iq4t_dot(const IQ4T &w, const i32x4 (&af)[4], uint32_t g)
+{
+    i32x4 d0 = {0, 0, 0, 0}, d1 = {0, 0, 0, 0};
+    d0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[0], iq4t_operand<false>(w.q0), d0, 0, 0, 0);
+    d1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[2], iq4t_operand<false>(w.q1), d1, 0, 0, 0);
+    d0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[1], iq4t_operand<true>(w.q0), d0, 0, 0, 0);
+    d1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[3], iq4t_operand<true>(w.q1), d1, 0, 0, 0);
+    float da, db;
+    iq4t_scales(w, g, da, db);
+    // three signed base-256 digits of the fixed-point activations: sum q*x' = S0 + 256*S1 + 65536*S2 (integers, exact)
+    const float v0 = fmaf((float)d0[2], 65536.0f, fmaf((float)d0[1], 256.0f, (float)d0[0]));
+    const float v1 = fmaf((float)d1[2], 65536.0f, fmaf((float)d1[1], 256.0f, (float)d1[0]));
+    return fmaf(db, v1, da * v0);
+}
+
 // ---- a step against several activation vectors (the batched decode): unpack once, then one dot per column ------------------------------
-// The part of q4t_dot / q5t_dot / q6t_dot / q8t_dot / q40t_dot / q3t_dot that does not depend on x, done once per step: the four B operands (one byte per
+// The part of q4t_dot / q5t_dot / q6t_dot / q8t_dot / q40t_dot / q3t_dot / iq4t_dot that does not depend on x, done once per step: the four B operands (one byte per
 // weight) and the scales.
 struct KqmW4 { i32x4 b[4]; float scv[2], mv[2]; };   // b[2n + hf]: low (n = 0) / high (n = 1) nibbles of q{hf}, the slot order of the A fragments
 struct KqmW6 { i32x4 b[4]; float sc[4]; float d; };  // b[qd], scales[8n + (G&1) + 2 qd] as floats
@@ -450,6 +507,22 @@ __device__ __forceinline__ KqmW4 kqm_unpack(const Q40T &w, uint32_t)
     return u;
 }
 
+// IQ4_XS: the operand of Q4_K's columns, in Q4_0's slot order.  b[] carries the table values of the codes (signed bytes, looked up once
+// per step for all columns), scv the two d * (ls - 32); there is no offset and no min: mv = 0, so kqm_dot(KqmW4) adds -0 * sums (nothing)
+// and is untouched.
+__device__ __forceinline__ KqmW4 kqm_unpack(const IQ4T &w, uint32_t g)
+{
+    KqmW4 u;
+    u.b[0] = iq4t_operand<false>(w.q0);
+    u.b[1] = iq4t_operand<true>(w.q0);
+    u.b[2] = iq4t_operand<false>(w.q1);
+    u.b[3] = iq4t_operand<true>(w.q1);
+    iq4t_scales(w, g, u.scv[0], u.scv[1]);
+    u.mv[0] = 0.f;
+    u.mv[1] = 0.f;
+    return u;
+}
+
 // Q8_0: the quants are the B operands as loaded (signed bytes); d of the lane's four 32-blocks 2h + (G >> 1) widened once.
 struct KqmW8 { i32x4 b[4]; float d[4]; };
 
@@ -509,8 +582,8 @@ __device__ __forceinline__ float kqm_dot(const KqmW8 &u, const i32x4 (&af)[4], f
 
 // Fixed-point staging of ONE 256-element super-block of the activation vector by one wave (lane holds elements 4*lane .. +3, after the
 // optional RMSNorm): power-of-two scale so that |x * 2^S| < 2^22, three signed base-256 digits per element written as MFMA A
-// fragments [blk][slot:4][G][digit][16 B] (Q4_K / Q5_K / Q4_0 layout in xa, Q6_K / Q3_K layout in xa6, Q8_0 layout in xa), the sums of x' per scale group
-// (K-quants only) and the exponent S (sexp[blk]; the consumer applies ldexpf(partial, -S)).  Nothing written here is read by another wave.
+// fragments [blk][slot:4][G][digit][16 B] (Q4_K / Q5_K / Q4_0 / IQ4_XS layout in xa, Q6_K / Q3_K layout in xa6, Q8_0 layout in xa), the sums of x' per scale group
+// (K-quants and Q4_0 only; IQ4_XS reads none) and the exponent S (sexp[blk]; the consumer applies ldexpf(partial, -S)).  Nothing written here is read by another wave.
 // S = 21 - ilogb(max|x|) for every finite non-zero maximum, fp32 subnormals (S up to 170) to FLT_MAX (S = -106) alike, and x is scaled
 // with ldexpf on the value, so neither 2^S nor 2^-S is ever formed as a float: every finite super-block keeps 22+ bits of its maximum.
 // An all-zero super-block stages zeros (S = 0).  Non-finite x is not supported: Inf / NaN in a super-block make its digits and sums

@@ -123,7 +123,7 @@ int check_shape(const char *what, const Tensor &t, uint64_t rows, uint64_t cols,
                     (unsigned long long)t.cols, (unsigned long long)rows, (unsigned long long)cols);
     if (!matrix && t.type != NFAI_F32) return fail(NFAI_ERR_UNSUPPORTED, "finalize: norm gain %s must be F32 (type %d)", what, t.type);
     if (matrix && t.type != NFAI_F16 && t.type != NFAI_F32 && !is_kquant(t.type))
-        return fail(NFAI_ERR_UNSUPPORTED, "finalize: matrix %s has ggml type %d; kernels exist for F16/F32/Q3_K/Q4_0/Q4_K/Q5_K/Q6_K/Q8_0", what, t.type);
+        return fail(NFAI_ERR_UNSUPPORTED, "finalize: matrix %s has ggml type %d; kernels exist for F16/F32/IQ4_XS/Q3_K/Q4_0/Q4_K/Q5_K/Q6_K/Q8_0", what, t.type);
     return NFAI_OK;
 }
 
@@ -206,7 +206,9 @@ static Op op_fn(int cls, std::function<hipError_t(hipStream_t)> f) { Op o; o.kin
 // its step has another register shape and epilogue than the mixed kernel's Q4_K branch, and no common file type mixes Q4_0 with
 // K-quants inside q|k|v: like Q8_0 it shares a launch only with other Q4_0 segments, every other type beside it gets a launch of
 // its own.  A Q3_K segment (Q3_K_M files: q and k in Q3_K beside a Q4_K or Q5_K v) stages as Q6_K does, with its own register shape
-// and epilogue: the same rule, it shares a launch only with other Q3_K segments.  qkv_launch: the launch that starts at segment `first` (-> `last`).
+// and epilogue: the same rule, it shares a launch only with other Q3_K segments.  An IQ4_XS segment stages as
+// Q4_K does, as Q4_0, with a register shape and an unpack (the codebook lookup) of its own: the same rule again (an IQ4_XS file keeps
+// attn_v in Q5_K when H / Hkv >= 4: two q|k|v launches per block then).  qkv_launch: the launch that starts at segment `first` (-> `last`).
 GemvArgs qkv_launch(Model *m, Layer &L, const float *x, int first, int &last)
 {
     const nfai_llama_desc &d = m->d;
@@ -705,14 +707,14 @@ static int set_tensor_impl(Model *m, const char *name, int type, uint64_t rows, 
     Tensor nt;
     nt.type = type; nt.rows = rows; nt.cols = cols; nt.bytes = rb * rows;
     hipStream_t s = m->ctx->stream;
-    if ((type == NFAI_Q8_0 || type == NFAI_Q5_K || type == NFAI_Q4_0 || type == NFAI_Q3_K) && (rows == 0 || rows % 16))
+    if ((type == NFAI_Q8_0 || type == NFAI_Q5_K || type == NFAI_Q4_0 || type == NFAI_Q3_K || type == NFAI_IQ4_XS) && (rows == 0 || rows % 16))
         return fail(NFAI_ERR_UNSUPPORTED, "set_tensor(%s): %s needs rows %% 16 == 0, cols %% 256 == 0 and cols <= 32768 (%llu x %llu)", name,
-                    type == NFAI_Q8_0 ? "Q8_0" : (type == NFAI_Q4_0 ? "Q4_0" : (type == NFAI_Q3_K ? "Q3_K" : "Q5_K")), (unsigned long long)rows, (unsigned long long)cols);
+                    type == NFAI_Q8_0 ? "Q8_0" : (type == NFAI_Q4_0 ? "Q4_0" : (type == NFAI_Q3_K ? "Q3_K" : (type == NFAI_IQ4_XS ? "IQ4_XS" : "Q5_K"))), (unsigned long long)rows, (unsigned long long)cols);
     const bool q4_t16 = type == NFAI_Q4_K && rows > 0 && rows % 16 == 0, q6_t16 = type == NFAI_Q6_K && rows > 0 && rows % 16 == 0;
-    const bool q8_t16 = type == NFAI_Q8_0, q5_t16 = type == NFAI_Q5_K, q40_t16 = type == NFAI_Q4_0, q3_t16 = type == NFAI_Q3_K;
+    const bool q8_t16 = type == NFAI_Q8_0, q5_t16 = type == NFAI_Q5_K, q40_t16 = type == NFAI_Q4_0, q3_t16 = type == NFAI_Q3_K, iq4_t16 = type == NFAI_IQ4_XS;
     auto fail_free = [&](void *a, void *b, int rc) { if (a) hipFree(a); if (b) hipFree(b); return rc; };
-    if (type == NFAI_Q6_K || q4_t16 || q8_t16 || q5_t16 || q40_t16 || q3_t16) {
-        // native blocks (host or device) -> owned repacked copy: Q6_K planes (common.h), Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 T16 tiles (kernels_gemv_kqm.hip)
+    if (type == NFAI_Q6_K || q4_t16 || q8_t16 || q5_t16 || q40_t16 || q3_t16 || iq4_t16) {
+        // native blocks (host or device) -> owned repacked copy: Q6_K planes (common.h), IQ4_XS / Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0 T16 tiles (kernels_gemv_kqm.hip)
         void *native = dev, *staged = nullptr;
         if (!dev) {
             int rc = dalloc(&staged, nt.bytes, s);
@@ -730,6 +732,7 @@ static int set_tensor_impl(Model *m, const char *name, int type, uint64_t rows, 
                      : q5_t16 ? launch_repack_q5k_t16(native, nt.ptr, rows, cols, s)
                      : q40_t16 ? launch_repack_q40_t16(native, nt.ptr, rows, cols, s)
                      : q3_t16 ? launch_repack_q3k_t16(native, nt.ptr, rows, cols, s)
+                     : iq4_t16 ? launch_repack_iq4xs_t16(native, nt.ptr, rows, cols, s)
                               : launch_repack_q6k(native, nt.ptr, rows * cols / 256, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return fail_free(staged, nt.ptr, fail(NFAI_ERR_HIP, "set_tensor(%s): K-quant repack failed: %s", name, hipGetErrorString(e)));
@@ -739,6 +742,7 @@ static int set_tensor_impl(Model *m, const char *name, int type, uint64_t rows, 
         if (q5_t16) nt.type = NFAI_Q5_K_T16;
         if (q40_t16) nt.type = NFAI_Q4_0_T16;
         if (q3_t16) nt.type = NFAI_Q3_K_T16;
+        if (iq4_t16) nt.type = NFAI_IQ4_XS_T16;
         if (staged) hipFree(staged);
     } else if (dev) {
         nt.ptr = dev;

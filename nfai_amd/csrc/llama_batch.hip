@@ -240,7 +240,7 @@ BatchKqArgs batch_kq(const BatchGemvArgs &a, int type)
     return k;
 }
 
-// q|k|v of block l: one launch for fp16 members; for quantised ones by weight type, in the fixed order Q4_K, Q5_K, Q6_K, Q8_0, Q4_0, Q3_K: one
+// q|k|v of block l: one launch for fp16 members; for quantised ones by weight type, in the fixed order Q4_K, Q5_K, Q6_K, Q8_0, Q4_0, Q3_K, IQ4_XS: one
 // launch when the three matrices agree, one per type when they differ (Q4_K_M and Q5_K_M files keep attn_v in Q6_K on half of the
 // blocks), so that a launch stages the activations in ONE fragment layout.  Returns the number of launches, three at the most.
 int batch_qkv(const BatchOps &ops, size_t l, BatchKqArgs (&out)[3])
@@ -253,7 +253,7 @@ int batch_qkv(const BatchOps &ops, size_t l, BatchKqArgs (&out)[3])
     const Layer &L = ops.bt->mem[0]->layers[l];
     const Tensor *t[3] = {&L.wq, &L.wk, &L.wv};
     int n = 0;
-    for (int type : {NFAI_Q4_K_T16, NFAI_Q5_K_T16, NFAI_Q6_K_T16, NFAI_Q8_0_T16, NFAI_Q4_0_T16, NFAI_Q3_K_T16}) {
+    for (int type : {NFAI_Q4_K_T16, NFAI_Q5_K_T16, NFAI_Q6_K_T16, NFAI_Q8_0_T16, NFAI_Q4_0_T16, NFAI_Q3_K_T16, NFAI_IQ4_XS_T16}) {
         BatchKqArgs k = batch_kq(base, type);
         int j = 0;
         for (int i = 0; i < 3; i++) { k.W[i] = nullptr; k.seg_rows[i] = 0; }
@@ -538,7 +538,7 @@ int profile_columns(Batch *bt, float *ms_by_class, uint32_t *launches_by_class, 
 
 // One model of a batch or window: what a batch admits as a member (i; the window's model is i = 0), in this order: finalized, a whole
 // model, the fused five-launch path, member 0's KV element type, matrix types (fp16 throughout, or with NFAI_BATCH_QUANT Q4_K / Q6_K
-// in the T16 layout throughout, with NFAI_BATCH_QUANT_ANY besides it Q5_K / Q8_0 / Q4_0 / Q3_K too, in any per-tensor mix), member 0's tensors.
+// in the T16 layout throughout, with NFAI_BATCH_QUANT_ANY besides it Q5_K / Q8_0 / Q4_0 / Q3_K / IQ4_XS too, in any per-tensor mix), member 0's tensors.
 // quant: the model's matrices are quantised.
 int admit_member(Model *m, Model *m0, uint32_t i, uint32_t flags, bool window, const char *fn, bool &quant)
 {
@@ -572,14 +572,14 @@ int admit_member(Model *m, Model *m0, uint32_t i, uint32_t flags, bool window, c
         if (t.type == NFAI_Q4_K || t.type == NFAI_Q6_K)
             return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu (ggml type %d, %llu rows) runs the VALU fallback (rows %% 16 != 0); the batched "
                                               "int8-MFMA kernels take 16-row tiles", fn, who, what, blk, ggml_type_of(t.type), (unsigned long long)t.rows);
-        if (allow_any && (t.type == NFAI_Q5_K || t.type == NFAI_Q8_0 || t.type == NFAI_Q4_0 || t.type == NFAI_Q3_K))
+        if (allow_any && (t.type == NFAI_Q5_K || t.type == NFAI_Q8_0 || t.type == NFAI_Q4_0 || t.type == NFAI_Q3_K || t.type == NFAI_IQ4_XS))
             return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu has ggml type %d in its native layout (the VALU fallback); the batched "
                                               "int8-MFMA kernels take the T16 layout", fn, who, what, blk, ggml_type_of(t.type));
         if (!allow_any && t.type != NFAI_Q4_K_T16 && t.type != NFAI_Q6_K_T16)
             return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu has ggml type %d; a quantised %s takes Q4_K and Q6_K matrices "
                                               "(Q5_K, Q8_0, Q4_0 and Q3_K weights decode through nfai_hip_llama_decode_step, or in a %s made with "
                                               "NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY)", fn, who, what, blk, ggml_type_of(t.type), obj, obj);
-        if (!is_t16(t.type)) return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu has ggml type %d; a quantised %s takes Q3_K, Q4_0, Q4_K, "
+        if (!is_t16(t.type)) return fail(NFAI_ERR_UNSUPPORTED, "%s: %s: %s of block %zu has ggml type %d; a quantised %s takes IQ4_XS, Q3_K, Q4_0, Q4_K, "
                                                                "Q5_K, Q6_K and Q8_0 matrices", fn, who, what, blk, ggml_type_of(t.type), obj);
         if (!firstq) { firstq = what; firstq_blk = blk; firstq_type = ggml_type_of(t.type); }
         return NFAI_OK;

@@ -5,9 +5,10 @@
 using namespace nfai;
 
 // Does the MFMA prefill widen a matrix of this type to fp16?  Every quantised one; under NFAI_PREFILL_FUSED=1 (Q4_K / Q6_K take
-// the dequant-in-LDS GEMM) only Q8_0, Q5_K, Q4_0 and Q3_K, which have no such GEMM.  A widened Q4_0 weight is d * (q - 8) rounded to fp16:
-// |d| * 8 must stay below 65504 there, as |d| * 127 must for Q8_0, and |d| * 32 * 4 for a widened Q3_K weight d * (sc - 32) * (q - 4).
-static bool prefill_widens(int type, bool fused) { return type != NFAI_F16 && (!fused || type == NFAI_Q8_0_T16 || type == NFAI_Q5_K_T16 || type == NFAI_Q4_0_T16 || type == NFAI_Q3_K_T16); }
+// the dequant-in-LDS GEMM) only Q8_0, Q5_K, Q4_0, Q3_K and IQ4_XS, which have no such GEMM.  A widened Q4_0 weight is d * (q - 8) rounded to fp16:
+// |d| * 8 must stay below 65504 there, as |d| * 127 must for Q8_0, and |d| * 32 * 4 for a widened Q3_K weight d * (sc - 32) * (q - 4),
+// and |d| * 32 * 127 for a widened IQ4_XS weight d * (ls - 32) * KV[q].
+static bool prefill_widens(int type, bool fused) { return type != NFAI_F16 && (!fused || type == NFAI_Q8_0_T16 || type == NFAI_Q5_K_T16 || type == NFAI_Q4_0_T16 || type == NFAI_Q3_K_T16 || type == NFAI_IQ4_XS_T16); }
 
 // One chunk of T prompt tokens through every block on the MFMA path (kernels_prefill.hip).  A pipeline stage (nfai_hip_llama_stage_ingest)
 // passes hidden_in ([T][E] fp32, device: the previous stage's rows) in place of tokens, and hidden_out ([T][E]) to take this stage's
@@ -162,7 +163,7 @@ static int prefill_chunk(Model *m, const uint32_t *tokens, uint32_t T, const flo
     for (Layer &Lq : m->layers) {
         Layer L = Lq;
         WideShadow &wd = *w.wide;
-        if (wd.ptr) {   // (NFAI_PREFILL_FUSED=1: allocated only for Q8_0 / Q5_K / Q4_0 / Q3_K matrices, ensure_wide_shadow)
+        if (wd.ptr) {   // (NFAI_PREFILL_FUSED=1: allocated only for Q8_0 / Q5_K / Q4_0 / Q3_K / IQ4_XS matrices, ensure_wide_shadow)
             const size_t li = (size_t)(&Lq - m->layers.data());
             const bool kept = wd.all && wd.done[li];  // widened by an earlier chunk / prefill and still current
             uint64_t off = wd.all ? li * wd.slot : 0;

@@ -12,7 +12,7 @@ factories in order (:36-42).  Differences, all on purpose:
     as sbyte and never applies the block scale (Parser.cs:93-99); other Q8_0 tensors still raise; Q5_K tensors likewise
     under Q5_K_RULE (the same rules; the reference has no Q5_K path at all, Parser.cs:111-114) and Q4_0 tensors under
     Q4_0_RULE (the same rules again; the reference throws for Q4_0, Parser.cs:111-114) and Q3_K tensors under Q3_K_RULE
-    (likewise);
+    (likewise), and IQ4_XS tensors under IQ4_XS_RULE (likewise);
   * shapes are returned as (rows, cols) = (ne1, ne0); the reference keeps GGUF order [ne0, ne1].
 `GGUFWriter` exists so tests and tools can build model files offline (no checkpoints here).
 """
@@ -36,20 +36,22 @@ GGML_F32, GGML_F16, GGML_Q8_0, GGML_Q4_K, GGML_Q6_K = 0, 1, 8, 12, 14
 GGML_Q5_K = 13
 GGML_Q4_0 = 2
 GGML_Q3_K = 11
+GGML_IQ4_XS = 23
 Q8_0_RULE = "Q8_0 needs a 2-D tensor with rows % 16 == 0, cols % 256 == 0 and cols <= 32768"
 Q4_0_RULE = "Q4_0 needs a 2-D tensor with rows % 16 == 0, cols % 256 == 0 and cols <= 32768"
 Q3_K_RULE = "Q3_K needs a 2-D tensor with rows % 16 == 0, cols % 256 == 0 and cols <= 32768"
+IQ4_XS_RULE = "IQ4_XS needs a 2-D tensor with rows % 16 == 0, cols % 256 == 0 and cols <= 32768"
 Q5_K_RULE = "Q5_K needs a 2-D tensor with rows % 16 == 0, cols % 256 == 0 and cols <= 32768"
 GGML_BLOCK = {0: (1, 4), 1: (1, 2), 2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24), 8: (32, 34), 9: (32, 36),
               10: (256, 84), 11: (256, 110), 12: (256, 144), 13: (256, 176), 14: (256, 210), 15: (256, 292),
-              24: (1, 1), 25: (1, 2), 26: (1, 4), 27: (1, 8), 28: (1, 8)}
+              23: (256, 136), 24: (1, 1), 25: (1, 2), 26: (1, 4), 27: (1, 8), 28: (1, 8)}
 GGML_NAME = {0: "float32", 1: "float16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 9: "Q8_1", 10: "Q2_K",
-             11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 15: "Q8_K", 24: "int8", 25: "int16", 26: "int32",
+             11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 15: "Q8_K", 23: "IQ4_XS", 24: "int8", 25: "int16", 26: "int32",
              27: "int64", 28: "float64"}
 
 
 def q8_0_shape_ok(shape) -> bool:
-    """GGUF shape [ne0, ne1] of a Q8_0 tensor the kernels take (Q8_0_RULE; Q5_K_RULE, Q4_0_RULE and Q3_K_RULE are the same)."""
+    """GGUF shape [ne0, ne1] of a Q8_0 tensor the kernels take (Q8_0_RULE; Q5_K_RULE, Q4_0_RULE, Q3_K_RULE and IQ4_XS_RULE are the same)."""
     return len(shape) == 2 and shape[1] > 0 and shape[1] % 16 == 0 and shape[0] % 256 == 0 and 0 < shape[0] <= 32768
 
 
@@ -174,8 +176,12 @@ class Parser:
             if q8_0_shape_ok(ti.shape):
                 return QuantTensor(raw, ti.ggml_type, (rows, cols))
             raise ValueError(f"Unsupported data type Q3_K for tensor {ti.name} (shape {list(ti.shape)}): {Q3_K_RULE}")
+        if ti.ggml_type == GGML_IQ4_XS:
+            if q8_0_shape_ok(ti.shape):
+                return QuantTensor(raw, ti.ggml_type, (rows, cols))
+            raise ValueError(f"Unsupported data type IQ4_XS for tensor {ti.name} (shape {list(ti.shape)}): {IQ4_XS_RULE}")
         raise ValueError(f"Unsupported data type {GGML_NAME.get(ti.ggml_type, ti.ggml_type)} for tensor {ti.name} "
-                         "(kernels exist for F32, F16, Q3_K, Q4_0, Q4_K, Q5_K, Q6_K, Q8_0)")
+                         "(kernels exist for F32, F16, IQ4_XS, Q3_K, Q4_0, Q4_K, Q5_K, Q6_K, Q8_0)")
 
     def Parse(self, modelOptions, **kw):
         import os

@@ -30,7 +30,7 @@ class ModelOptions:
 
 @dataclass
 class QuantTensor:
-    """A GGUF tensor kept in its on-disk block encoding (Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0): raw bytes + logical shape."""
+    """A GGUF tensor kept in its on-disk block encoding (IQ4_XS / Q3_K / Q4_0 / Q4_K / Q5_K / Q6_K / Q8_0): raw bytes + logical shape."""
     data: np.ndarray  # uint8
     ggml_type: int
     shape: tuple  # (rows, cols) = (ne1, ne0)
@@ -156,7 +156,7 @@ class LlamaModel:
         self.handle = h
         self._keep = []
         self._quantized = bool(getattr(share_from, "_quantized", False))   # any matrix in a block encoding (picks the window's kernel family)
-        self._any_quant = bool(getattr(share_from, "_any_quant", False))   # any matrix in Q5_K / Q8_0 / Q4_0 / Q3_K (the window then needs BATCH_QUANT_ANY)
+        self._any_quant = bool(getattr(share_from, "_any_quant", False))   # any matrix in Q5_K / Q8_0 / Q4_0 / Q3_K / IQ4_XS (the window then needs BATCH_QUANT_ANY)
         self._windows = {}
         if share_from is not None:  # another slot of the same pipeline stage: the donor's weights, no copy, no second repack
             self._donor = share_from
@@ -171,14 +171,14 @@ class LlamaModel:
             ptr, ty, rows, cols = t
             if rows > 1 and ty not in (_lib.F32, _lib.F16):
                 self._quantized = True
-                if ty in (_lib.Q5_K, _lib.Q8_0, _lib.Q4_0, _lib.Q3_K):
+                if ty in (_lib.Q5_K, _lib.Q8_0, _lib.Q4_0, _lib.Q3_K, _lib.IQ4_XS):
                     self._any_quant = True
             call("nfai_hip_llama_set_tensor_device", self.handle, name.encode(), ty, rows, cols, C.c_void_p(ptr))
             return
         if isinstance(t, QuantTensor):
             self._quantized = True
             a, ty, (rows, cols) = np.ascontiguousarray(t.data), t.ggml_type, t.shape
-            if ty in (_lib.Q5_K, _lib.Q8_0, _lib.Q4_0, _lib.Q3_K):
+            if ty in (_lib.Q5_K, _lib.Q8_0, _lib.Q4_0, _lib.Q3_K, _lib.IQ4_XS):
                 self._any_quant = True
         else:
             a = np.ascontiguousarray(t)
@@ -414,8 +414,8 @@ class LlamaModel:
 class LlamaBatch:
     """n LlamaModel instances over ONE set of weights advancing together: what n concurrent token loops (LlamaModel.cs:116-125) do,
     with every weight row read once per step (nfai_hip_llama_batch_*).  `models`: 1 to 8 whole fp16 models (quantized=True: or
-    1 to 8 whole models whose matrices are all Q4_K / Q6_K; with any_quant=True besides it: Q5_K, Q8_0, Q4_0 and Q3_K matrices too, in any
-    per-tensor mix of the six) on one buffer manager,
+    1 to 8 whole models whose matrices are all Q4_K / Q6_K; with any_quant=True besides it: Q5_K, Q8_0, Q4_0, Q3_K and IQ4_XS matrices too, in any
+    per-tensor mix of the seven) on one buffer manager,
     one of them the donor of the others (`share_from`).  Each member keeps its own KV cache and position and stays a normal
     LlamaModel: Step / Ingest / SetPos on a member between batch steps are seen by the next batch step.
     wide=True: 1 to 16 whole fp16 models on the fp16-MFMA kernels (nfai_hip_llama_batch_create_wide); every method works on it with

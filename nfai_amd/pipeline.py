@@ -477,10 +477,11 @@ def pipeline_costs(dims, quant: str) -> tuple[float, float]:
     matrix in Q8_0, 8.5 bits per weight (34 bytes per 32).  "q5_k_m": Q5_K (5.5 bits, 176 bytes per 256) in the mix of
     synth.q5_k_m_type, Q6_K where it puts it.  "q4_0": Q4_0 (4.5 bits, 18 bytes per 32) in the mix of synth.q4_0_type (the
     lm_head in Q6_K).  "q3_k_m": Q3_K (3.4375 bits, 110 bytes per 256) in the mix of synth.q3_k_type, Q4_K / Q5_K / Q6_K where
-    it puts them, block by block (the average block is used)."""
+    it puts them, block by block (the average block is used).  "iq4_xs": IQ4_XS (4.25 bits, 136 bytes per 256) in the mix of
+    synth.iq4_xs_type, Q5_K / Q6_K where it puts them (the average block is used)."""
     import bench as B
-    from .synth import q3_k_type, q4_0_type, q5_k_m_type
-    bits = {1: 16.0, 2: 4.5, 11: 3.4375, B.Q4_K: 4.5, B.Q6_K: 6.5625, 8: 8.5, 13: 5.5}
+    from .synth import iq4_xs_type, q3_k_type, q4_0_type, q5_k_m_type
+    bits = {1: 16.0, 2: 4.5, 11: 3.4375, B.Q4_K: 4.5, B.Q6_K: 6.5625, 8: 8.5, 13: 5.5, 23: 4.25}
     if quant == "q8_0":
         type_of = lambda name: 8
     elif quant == "q5_k_m":
@@ -489,6 +490,8 @@ def pipeline_costs(dims, quant: str) -> tuple[float, float]:
         type_of = lambda name: q4_0_type(name, dims)
     elif quant == "q3_k_m":
         type_of = lambda name: q3_k_type(name, dims)
+    elif quant == "iq4_xs":
+        type_of = lambda name: iq4_xs_type(name, dims)
     else:
         type_of = lambda name: B.tensor_type(name, dims, quant)
     tot = 0.0

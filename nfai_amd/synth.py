@@ -236,6 +236,97 @@ def q3_k_type(name: str, dims, mix: str = "q3_k_m", layer_offset: int = 0, n_lay
     return 11
 
 
+IQ4_KV = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], np.int8)   # the IQ4_XS / IQ4_NL codebook
+
+
+def _iq4_xs_scales(b):
+    """The eight 6-bit scales ls (0..63) of every IQ4_XS block in b [nb][136]: low nibble of scale ib from nibble ib % 2 of
+    scales_l[ib // 2], its high two bits from bits 2 ib .. + 1 of the uint16 scales_h."""
+    sh = b[:, 2:4].copy().view(np.uint16).astype(np.int32)                                    # [nb][1]
+    sl = b[:, 4:8].astype(np.int32)
+    ib = np.arange(8)
+    lo = (sl[:, ib // 2] >> (4 * (ib % 2))[None, :]) & 0xF
+    hi = (sh >> (2 * ib)[None, :]) & 3
+    return lo | (hi << 4)
+
+
+def dequantize_iq4_xs(raw, rows: int, cols: int) -> np.ndarray:
+    """ggml block_iq4_xs (fp16 d, uint16 scales_h, scales_l[4], qs[128] per 256 weights: 136 bytes) dequantised as restated from
+    the format: float32 [rows][cols].  Sub-block ib (32 weights) has the 6-bit scale ls of _iq4_xs_scales and dl = d * (ls - 32);
+    weight 32 ib + j = dl * KV[qs[16 ib + j] & 0xF], weight 32 ib + 16 + j = dl * KV[qs[16 ib + j] >> 4] (j < 16) with the
+    16-entry table IQ4_KV, both products rounded to fp32.  The restatement was written without ggml's source at hand: check it
+    against a real IQ4_XS file when one is available."""
+    b = np.frombuffer(bytes(raw), np.uint8).reshape(-1, 136)
+    nb = b.shape[0]
+    d = b[:, 0:2].copy().view(np.float16).astype(np.float32)                                  # [nb][1]
+    dl = (d * (_iq4_xs_scales(b) - 32).astype(np.float32)).astype(np.float32)                 # [nb][8]
+    qs = b[:, 8:136].reshape(nb, 8, 16)
+    codes = np.concatenate([qs & 0xF, qs >> 4], axis=2)                                       # [nb][ib][32]
+    y = dl[:, :, None] * IQ4_KV[codes].astype(np.float32)
+    return y.astype(np.float32).reshape(rows, cols)
+
+
+def quantize_iq4_xs(W) -> bytes:
+    """Valid ggml block_iq4_xs for every row of W [rows][cols] (cols % 256 == 0): 136 bytes per 256 weights in the order fp16 d,
+    uint16 scales_h, scales_l[4], qs[128].  NOT llama.cpp's quantiser (its search over scales is not restated).  Per sub-block of
+    32 the signed step is s = m / -127 with m the value of largest magnitude with its sign (the first among equals), so that the
+    extreme lands on code 0 (KV[0] = -127); d = max|s| / 31 as the next fp16 at or above it; ls - 32 = s / d rounded AWAY from
+    zero and clipped to +-31; every weight takes the table entry nearest x / (d (ls - 32)) (the lower code among equals).  As the
+    step |d (ls - 32)| is never below |s|, x / step lies in [-127, 127]; the largest half-gap of the table is 12 (between 89 and
+    113) and a value above 113 is at most 14 from it, so every weight decodes within 14 steps |d (ls - 32)| of its value: a bound
+    derived from the table, not measured.  A sub-block of zeros stores ls = 32 and code 8, an all-zero block d = 0.  A fixed point
+    on its own output, dequantize(quantize(y)) == y for y = dequantize(quantize(W)), in every sub-block that holds code 0 (its
+    extreme then decodes to -127 steps and gives the step back: d (ls - 32) has 16 significant bits, so 127 times it is exact
+    in fp32); the block's largest sub-block always does (ls - 32 = +-31: d comes back exactly)."""
+    x = np.asarray(W, dtype=np.float32).reshape(-1, 8, 32)                                    # [nb][ib][j]
+    nb = x.shape[0]
+    idx = np.argmax(np.abs(x), axis=2)
+    m = np.take_along_axis(x, idx[:, :, None], axis=2)[:, :, 0]
+    s = (m / np.float32(-127)).astype(np.float32)
+    d = _f16_up(np.abs(s).max(axis=1) / np.float32(31))
+    d32 = d.astype(np.float32)
+    ok = d32 > 0
+    k = np.where(ok[:, None], np.ceil(np.abs(s) / np.where(ok, d32, 1)[:, None]), 0).astype(np.float32)
+    k = np.minimum(k + (d32[:, None] * k < np.abs(s)), 31)                                    # (a quotient rounded down onto an integer)
+    ls = (np.sign(s) * k).astype(np.int32)                                                    # ls - 32
+    step = d32[:, None] * ls.astype(np.float32)                                               # d * (ls - 32) as the decoder forms it
+    t = np.where(step[:, :, None] != 0, x / np.where(step != 0, step, 1)[:, :, None], 0).astype(np.float32)
+    codes = np.argmin(np.abs(t[..., None] - IQ4_KV.astype(np.float32)), axis=3).astype(np.uint8)   # [nb][8][32], first among equals
+    ls6 = (ls + 32).astype(np.uint16)
+    out = np.zeros((nb, 136), np.uint8)
+    out[:, 0:2] = d.view(np.uint8).reshape(nb, 2)
+    sh = np.zeros(nb, np.uint16)
+    for ib in range(8):
+        sh |= (ls6[:, ib] >> 4) << (2 * ib)
+        out[:, 4 + ib // 2] |= ((ls6[:, ib] & 0xF) << (4 * (ib % 2))).astype(np.uint8)
+    out[:, 2:4] = sh.view(np.uint8).reshape(nb, 2)
+    out[:, 8:136] = (codes[:, :, :16] | (codes[:, :, 16:] << 4)).reshape(nb, 128)
+    return out.tobytes()
+
+
+def iq4_xs_type(name: str, dims, mix: str = "iq4_xs", layer_offset: int = 0, n_layers_file: int | None = None) -> int:
+    """ggml type of a matrix in an IQ4_XS file.  mix="iq4_xs": IQ4_XS (23) for every matrix, except Q5_K (13) for attn_v when the
+    model groups its heads H / Hkv >= 4, Q5_K for ffn_down in the first n_layer // 8 blocks, and Q6_K (14) for the lm_head
+    (output.weight, or a tied token_embd); an untied token_embd is IQ4_XS.  This is llama.cpp's rule for the file type as
+    recalled: its source was not at hand when this was written, so check it against a real file before relying on it.
+    mix="all_iq4_xs": every matrix IQ4_XS, the head and the embedding table too (so that the IQ4_XS lm_head + ArgMax and embedding
+    gather run).  layer_offset / n_layers_file: a pipeline stage's blocks numbered within the whole file."""
+    if mix == "all_iq4_xs":
+        return 23
+    if mix != "iq4_xs":
+        raise ValueError(f"unknown IQ4_XS mix {mix!r} (iq4_xs, all_iq4_xs)")
+    if name == "output.weight" or (name == "token_embd.weight" and dims.tied):
+        return 14
+    if not name.startswith("blk."):
+        return 23
+    layer, n_layer = int(name.split(".")[1]) + layer_offset, n_layers_file or dims.L
+    if name.endswith("attn_v.weight"):
+        return 13 if dims.H // dims.Hkv >= 4 else 23
+    if name.endswith("ffn_down.weight"):
+        return 13 if layer < n_layer // 8 else 23
+    return 23
+
+
 def _f16_up(v):
     """The smallest fp16 values >= v (v >= 0, float32 array): a scale that a 6-bit code times it must still reach v."""
     h = np.asarray(v, np.float32).astype(np.float16)

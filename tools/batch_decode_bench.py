@@ -22,8 +22,8 @@ the oracle, which takes about a minute of host time).  One JSON line; --out writ
 for token_embd / output and for attn_v / ffn_down of the blocks llama.cpp keeps there), through the int8-MFMA batch
 (LlamaBatch(..., quantized=True), nfai_hip_llama_batch_create_ex); the oracle walks the dequantised weights.
 
---quant q5_k_m | q8_0 | q4_0 | q3_k_m: the same on the Q5_K_M mix of tools/q5_k_bench.py, the Q8_0 weights of tools/q8_0_bench.py, the
-Q4_0 mix of tools/q4_0_bench.py and the Q3_K_M mix of tools/q3_k_bench.py (their generators), through LlamaBatch(..., quantized=True, any_quant=True) (NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY).
+--quant q5_k_m | q8_0 | q4_0 | q3_k_m | iq4_xs: the same on the Q5_K_M mix of tools/q5_k_bench.py, the Q8_0 weights of tools/q8_0_bench.py, the
+Q4_0 mix of tools/q4_0_bench.py, the Q3_K_M mix of tools/q3_k_bench.py and the IQ4_XS mix of tools/iq4_xs_bench.py (their generators), through LlamaBatch(..., quantized=True, any_quant=True) (NFAI_BATCH_QUANT | NFAI_BATCH_QUANT_ANY).
 
     python tools/batch_decode_bench.py --quant q5_k_m --out profiles/batch_decode_q5_k_m.json
     python tools/batch_decode_bench.py --quant q8_0 --out profiles/batch_decode_q8_0.json
@@ -90,7 +90,7 @@ def spread(xs):
     return (max(xs) - min(xs)) / statistics.median(xs)
 
 
-ANY_QUANT = ("q5_k_m", "q8_0", "q4_0", "q3_k_m")   # the encodings a batch takes with any_quant=True
+ANY_QUANT = ("q5_k_m", "q8_0", "q4_0", "q3_k_m", "iq4_xs")   # the encodings a batch takes with any_quant=True
 
 
 def gen_weights(torch, dims, quant):
@@ -107,6 +107,9 @@ def gen_weights(torch, dims, quant):
     if quant == "q3_k_m":
         import q3_k_bench
         return q3_k_bench.gen_q3_k_weights_hbm(torch, dims)
+    if quant == "iq4_xs":
+        import iq4_xs_bench
+        return iq4_xs_bench.gen_iq4_xs_weights_hbm(torch, dims)
     import bench as B
     return B.gen_weights_hbm(torch, dims, (0, dims.L), True, True, quant=quant)
 
@@ -122,6 +125,9 @@ def host_weights(weights, quant):
     if quant == "q3_k_m":
         import q3_k_bench
         return {k: q3_k_bench.dequant(t, ty, r, c) for k, (t, ty, r, c) in weights.items()}
+    if quant == "iq4_xs":
+        import iq4_xs_bench
+        return {k: iq4_xs_bench.dequant(t, ty, r, c) for k, (t, ty, r, c) in weights.items()}
     if quant == "q8_0":
         import q8_0_bench
         return {k: (q8_0_bench.dequant_q8_0(t.cpu().numpy(), r, c) if ty == q8_0_bench.Q8_0 else t.cpu().numpy()) for k, (t, ty, r, c) in weights.items()}
@@ -512,7 +518,7 @@ def main():
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--only", default="", metavar="MODEL", help="one model, e.g. llama-3.2-3b")
-    ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m", "q5_k_m", "q8_0", "q4_0", "q3_k_m"], help="weight encoding (all but f16: the int8-MFMA batch)")
+    ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m", "q5_k_m", "q8_0", "q4_0", "q3_k_m", "iq4_xs"], help="weight encoding (all but f16: the int8-MFMA batch)")
     ap.add_argument("--sampled", action="store_true", help="the default sampler on a batch (StepTopK) instead of the greedy comparison")
     ap.add_argument("--wide", action="store_true", help="the wide batch (up to 16 members, fp16 MFMA) against the existing one")
     ap.add_argument("--out", default=None)

@@ -22,7 +22,8 @@ What is NOT measured: how often an n-gram drafter is right on real text.  The we
     python tools/spec_decode_bench.py --quant q4_k_m --out profiles/spec_decode_q4_k_m.json
     python tools/spec_decode_bench.py --depth 8192 --only llama-3.2-3b --out profiles/spec_decode_deep.json
 
---quant q5_k_m | q8_0 | q4_0 | q3_k_m: the weights of tools/q5_k_bench.py / tools/q8_0_bench.py / tools/q4_0_bench.py / tools/q3_k_bench.py, window and batch made with any_quant=True.
+--quant q5_k_m | q8_0 | q4_0 | q3_k_m | iq4_xs: the weights of tools/q5_k_bench.py / tools/q8_0_bench.py / tools/q4_0_bench.py / tools/q3_k_bench.py /
+tools/iq4_xs_bench.py, window and batch made with any_quant=True.
 """
 import argparse
 import json
@@ -183,7 +184,7 @@ def main():
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--depth", type=int, default=512, help="tokens ingested before the measurement (8192: the deep-context run)")
     ap.add_argument("--only", default="", metavar="MODEL", help="one model, e.g. llama-3.2-3b")
-    ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m", "q5_k_m", "q8_0", "q4_0", "q3_k_m"])
+    ap.add_argument("--quant", default="f16", choices=["f16", "q4_k_m", "q5_k_m", "q8_0", "q4_0", "q3_k_m", "iq4_xs"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
